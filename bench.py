@@ -9,10 +9,15 @@ scales 3 + rotations 4 + features 11 floats, all-gather of each view's 3-float S
 the 48-float SH gradient sum rebuilt on every rank) -- view-parallel data parallelism, every rank
 renders its own camera of the same scene (weak scaling).
 
-    python bench.py [--gpus N] [--steps K] [--warmup W]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
     python -m torch.distributed.run --nproc-per-node N --master-addr 127.0.0.1 ... bench.py --gpus N
 
-Rank 0 prints one JSON line. `roofline` prices renderCUDA fwd + bwd -- render_fwd_glds_kernel and
+Rank 0 prints one JSON line. A plain run sets up, warms up, times the K steps and prints the headline
+figure (`value`, `ms_per_step`) alone. `--dump-outputs DIR` also writes what the last timed step
+returned (forward images, backward gradients) as DIR/<name>.npy, float32; an array of more than
+DUMP_CAP elements is stored as a fixed, seeded sample of its elements, so that two builds can be
+compared output for output. Everything below is measured only with `--full`, in runs of its own
+after the timed steps. `roofline` prices renderCUDA fwd + bwd -- render_fwd_glds_kernel and
 render_bwd_glds_kernel with its atomic second stage (plus the sums' memset; row_sum_kernel instead
 with the rows reduction, R3DG_BWD_REDUCE=rows) -- with SURVEY.md
 §8d's algorithmic bytes exactly (272*L + 156*H*W + 16*tiles at S=11; the 12*L the forward also moves
@@ -41,6 +46,37 @@ sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md chip table (8.0 TB/s spec)
 P_M1, W_M1, H_M1, S_M1 = 1_000_000, 1920, 1080, 11
+# --dump-outputs: elements kept per array (20 arrays x 3 MB stay under 64 MB in all)
+DUMP_CAP = 750_000
+FWD_NAMES = ["num_rendered", "n_contrib", "color", "opacity", "depth", "stencil", "feature", "shader_color", "normal",
+             "surface_xyz", "radii"]
+BWD_NAMES = ["dL_dmeans2D", "dL_dcolors", "dL_dopacity", "dL_dmeans3D", "dL_dfeatures", "dL_dcov3D", "dL_dsh",
+             "dL_dscales", "dL_drotations"]
+
+
+def dump_outputs(path: str, fwd, bwd) -> None:
+    """The last timed step's outputs as <path>/<name>.npy (float32): the forward tuple's images and
+    radii, the backward 9-tuple. Arrays above DUMP_CAP elements keep a seeded sample of their
+    flattened elements (the same indices for the same shape in every run); empty outputs (no
+    colours / cov3D given) are left out."""
+    import torch
+
+    os.makedirs(path, exist_ok=True)
+    named = list(zip(FWD_NAMES, fwd)) + list(zip(BWD_NAMES, bwd))
+    total = 0
+    for name, v in named:
+        if not torch.is_tensor(v):
+            v = torch.as_tensor([v])
+        if v.numel() == 0:
+            continue
+        v = v.detach()
+        if v.numel() > DUMP_CAP:
+            idx = np.random.default_rng(v.numel()).integers(0, v.numel(), DUMP_CAP)
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+        a = v.to(torch.float32).cpu().numpy()
+        total += a.nbytes
+        np.save(os.path.join(path, name + ".npy"), a)
+    assert total <= 64 << 20, total
 
 
 def algorithmic_bytes(L: int, npix: int, tiles: int, S: int) -> tuple[int, int]:
@@ -313,7 +349,12 @@ def main() -> None:
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--P", type=int, default=P_M1)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's outputs as DIR/<name>.npy (rank 0)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also measure the per-kernel / roofline figures, the exchange "
+                         "probe (N > 1), the BVH tracer and the CPU baselines")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
     ap.add_argument("--chunks", type=int, default=4, help="gradient exchange chunks (N > 1)")
     ap.add_argument("--opt", action="append", default=[], metavar="NAME=VALUE",
                     help="library option (r3dg_set_options, include/r3dg_hip.h) for A/B runs, e.g. test_no_cull=1")
@@ -358,6 +399,9 @@ def main() -> None:
     g_depth = t(rng.normal(size=(H, W)) * 1e-3)
     g_feat = t(rng.normal(size=(S_M1, H, W)) * 1e-3)
 
+    keep = rank == 0 and args.dump_outputs is not None
+    last = {}
+
     def step(exchange=True):
         out = _C.rasterize_gaussians(bg, 0.0, 0.0, means3D, feats, empty, opac, scales, rots, 1.0, empty, view,
                                      view_inv, proj, proj_inv, cam.tanfovx, cam.tanfovy, cam.cx, cam.cy, H, W, sh, 3,
@@ -365,14 +409,16 @@ def main() -> None:
         L, radii, geom, binning, img = out[0], out[10], out[11], out[12], out[13]
         if world > 1 and exchange:
             # per-Gaussian gradients all-reduced chunk by chunk, overlapped with the gather phase
-            view_parallel.backward_all_reduce(
+            grads = view_parallel.backward_all_reduce(
                 _C, (bg, means3D, feats, radii, empty, scales, rots, 1.0, empty, view, proj, cam.tanfovx,
                      cam.tanfovy, g_color, g_opac, g_depth, g_feat, sh, 3, campos, geom, L, binning, img, True,
                      False, H, W, False, False), n_chunks=args.chunks)
         else:
-            _C.rasterize_gaussians_backward(bg, means3D, feats, radii, empty, scales, rots, 1.0, empty, view,
-                                            proj, cam.tanfovx, cam.tanfovy, g_color, g_opac, g_depth, g_feat,
-                                            sh, 3, campos, geom, L, binning, img, True, False)
+            grads = _C.rasterize_gaussians_backward(bg, means3D, feats, radii, empty, scales, rots, 1.0, empty, view,
+                                                    proj, cam.tanfovx, cam.tanfovy, g_color, g_opac, g_depth, g_feat,
+                                                    sh, 3, campos, geom, L, binning, img, True, False)
+        if keep:
+            last["fwd"], last["bwd"] = out[:len(FWD_NAMES)], grads
         return L
 
     def run(fn, k):
@@ -391,8 +437,11 @@ def main() -> None:
     for _ in range(args.warmup):
         L = step()
     elapsed, L = run(step, args.steps)
+    if keep:
+        dump_outputs(args.dump_outputs, last.pop("fwd"), last.pop("bwd"))
+        keep = False
     exchange = None
-    if world > 1:
+    if world > 1 and args.full:
         # outside the timed region: the same steps without the gradient exchange (each rank's
         # compute alone, max over ranks) and the two collectives alone at this size
         t_comp, _ = run(lambda: step(exchange=False), args.steps)
@@ -400,15 +449,17 @@ def main() -> None:
         dist.all_reduce(tc, op=dist.ReduceOp.MAX)
         t_comp = float(tc.item())
         exchange = comm_probe(list(view_parallel.LAST_COLLECTIVES["sequence"]), dev, world, backend)
-    # per-kernel device times: K more steps with HIP events inside the profiled launches (kept out
-    # of the timed region above)
-    _C.profile_enable(args.steps + 1)
-    for _ in range(args.steps):
-        step()
-    torch.cuda.synchronize()
-    prof = {k: _C.profile_read(i) for i, k in enumerate(["render_fwd", "render_bwd", "gather_bwd", "sort",
-                                                          "preprocess", "row_sum"])}
-    _C.profile_enable(0)
+    prof = None
+    if args.full:
+        # per-kernel device times: K more steps with HIP events inside the profiled launches (kept out
+        # of the timed region above)
+        _C.profile_enable(args.steps + 1)
+        for _ in range(args.steps):
+            step()
+        torch.cuda.synchronize()
+        prof = {k: _C.profile_read(i) for i, k in enumerate(["render_fwd", "render_bwd", "gather_bwd", "sort",
+                                                              "preprocess", "row_sum"])}
+        _C.profile_enable(0)
     if world > 1:
         te = torch.tensor([elapsed], dtype=torch.float64, device=dev)
         dist.all_reduce(te, op=dist.ReduceOp.MAX)
@@ -420,23 +471,6 @@ def main() -> None:
     ms_step = elapsed / args.steps * 1e3
     npix = H * W
     value = world * npix * args.steps / elapsed / 1e6
-    tiles = ((W + 15) // 16) * ((H + 15) // 16)
-    bf, bb = algorithmic_bytes(L, npix, tiles, S_M1)
-    # per-step device time of each stage
-    avg = {k: v[1] / args.steps for k, v in prof.items()}
-    launch = {k: (v[1] / v[0] if v[0] else 0.0) for k, v in prof.items()}
-    # renderCUDA fwd + bwd: the backward blend AND its per-instance reduction's second stage (the
-    # default atomic flush: the sums are zeroed inside render_fwd, the slot is empty; rows reduction:
-    # row_sum_kernel, which sums the partial rows the reference accumulates with atomics,
-    # backward.cu:552-611)
-    reduce_mode = "rows" if _C.get_options()["bwd_reduce"] == 1 else "atomic"
-    t_kern = (launch["render_fwd"] + launch["render_bwd"] + launch["row_sum"]) / 1e3
-    achieved = (bf + bb) / t_kern / 1e9
-    traffic = None
-    tr = load_traffic()
-    if tr and tr.get("config") == f"M1 P={args.P}":
-        traffic = tr.get("render_fwd_bytes", 0) + tr.get("render_bwd_bytes", 0) + tr.get("row_sum_bytes", 0)
-    valu = valu_roofline(load_valu(args.P), launch)
     res = {
         "metric": "Mpix/s fwd+bwd, 1M Gaussians @1920x1080; views/s at 1/2/4/8 MI355X",
         "value": round(value, 3),
@@ -458,6 +492,32 @@ def main() -> None:
                                   f"{args.chunks} chunks overlapped with the gather phase, 2 collectives per chunk "
                                   f"+ 1 camera-centre all-gather per step)"},
         "views_per_s": round(world * args.steps / elapsed, 3),
+    }
+    if args.dump_outputs is not None:
+        res["outputs"] = args.dump_outputs
+    if not args.full:
+        print(json.dumps(res), flush=True)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    tiles = ((W + 15) // 16) * ((H + 15) // 16)
+    bf, bb = algorithmic_bytes(L, npix, tiles, S_M1)
+    # per-step device time of each stage
+    avg = {k: v[1] / args.steps for k, v in prof.items()}
+    launch = {k: (v[1] / v[0] if v[0] else 0.0) for k, v in prof.items()}
+    # renderCUDA fwd + bwd: the backward blend AND its per-instance reduction's second stage (the
+    # default atomic flush: the sums are zeroed inside render_fwd, the slot is empty; rows reduction:
+    # row_sum_kernel, which sums the partial rows the reference accumulates with atomics,
+    # backward.cu:552-611)
+    reduce_mode = "rows" if _C.get_options()["bwd_reduce"] == 1 else "atomic"
+    t_kern = (launch["render_fwd"] + launch["render_bwd"] + launch["row_sum"]) / 1e3
+    achieved = (bf + bb) / t_kern / 1e9
+    traffic = None
+    tr = load_traffic()
+    if tr and tr.get("config") == f"M1 P={args.P}":
+        traffic = tr.get("render_fwd_bytes", 0) + tr.get("render_bwd_bytes", 0) + tr.get("row_sum_bytes", 0)
+    valu = valu_roofline(load_valu(args.P), launch)
+    res.update({
         # priced against HBM (north_star: no dense contraction, the blend's bytes over 8 TB/s); which
         # resource binds is derived from the measured fractions (DESIGN.md §4 "Can 0.40 be reached")
         "roofline": {"bound": "hbm", "priced_against": "hbm",
@@ -480,7 +540,7 @@ def main() -> None:
                                  if not prof["row_sum"][0] else "hipMemsetAsync of the per-Gaussian sums + the atomic "
                                  "flush inside render_bwd")
                        if reduce_mode == "atomic" else "row_sum_kernel over the partial rows"},
-    }
+    })
     if exchange is not None:
         res["collectives_per_step"] = exchange["collectives_per_step"]
         ms_comp = t_comp / args.steps * 1e3

@@ -23,7 +23,7 @@ def test_bench_two_ranks_gloo():
     env = dict(os.environ, R3DG_DIST_BACKEND="gloo", OMP_NUM_THREADS="4")
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr",
            "127.0.0.1", "--master-port", str(port), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--P", "20000",
-           "--steps", "2", "--warmup", "1", "--no-cpu-baseline"]
+           "--steps", "2", "--warmup", "1", "--full", "--no-cpu-baseline"]
     r = subprocess.run(cmd, cwd=ROOT, env=env, capture_output=True, text=True, timeout=360)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -8,7 +8,7 @@ sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import bench  # noqa: E402
 import relightable3dgaussian_amd as r3  # noqa: E402
 
-sys.argv = ["bench.py", "--steps", "1", "--warmup", "0", "--no-cpu-baseline"]
+sys.argv = ["bench.py", "--steps", "1", "--warmup", "0", "--full", "--no-cpu-baseline"]
 bench.main()
 lib = ctypes.CDLL(os.path.join(r3.LIB_DIR, "libr3dg_hip.so"))
 buf, fb = (ctypes.c_ulonglong * 8)(), (ctypes.c_ulonglong * 8)()

@@ -21,7 +21,7 @@ fi
 for i in $(seq 1 $NB); do
   for n in base $names; do
     if [ $n = base ]; then lib=""; else lib="R3DG_LIB_DIR=exp/$n/lib"; fi
-    env $lib timeout -k 10 150 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/${n}_$i.json 2> $OUT/${n}_$i.err; ok $?
+    env $lib timeout -k 10 150 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > $OUT/${n}_$i.json 2> $OUT/${n}_$i.err; ok $?
     python -c "import json; d=json.load(open('$OUT/${n}_$i.json')); print('$n', d['ms_per_step'], d['kernel_ms'], d['roofline']['frac'])" || tail -5 $OUT/${n}_$i.err
   done
 done

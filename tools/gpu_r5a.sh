@@ -10,5 +10,5 @@ timeout -k 10 120 /tmp/vexp_cr > $OUT/vexp.json; ok $?
 head -c 1500 $OUT/vexp.json
 R3DG_GRAD_REPORT=$OUT/grad.jsonl timeout -k 10 1000 python -u -m pytest tests -m gpu -v -s --timeout 300 --timeout-method thread > $OUT/pytest.log 2>&1; ok $?
 grep -E "passed|failed" $OUT/pytest.log | tail -3
-timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err; ok $?
+timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err; ok $?
 python -c "import json; d=json.load(open('$OUT/bench.json')); print(d['value'], d['ms_per_step'], d['kernel_ms'], d['roofline']['frac'])"

@@ -17,7 +17,7 @@ grep -E "passed|failed" $OUT/pytest.log | tail -3
 for rep in 1 2; do
   for n in base $names; do
     if [ $n = base ]; then lib=""; else lib="R3DG_LIB_DIR=exp/$n/lib"; fi
-    env $lib timeout -k 10 150 python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/${n}_$rep.json 2> $OUT/${n}_$rep.err; ok $?
+    env $lib timeout -k 10 150 python bench.py --steps 20 --warmup 3 --full --no-cpu-baseline > $OUT/${n}_$rep.json 2> $OUT/${n}_$rep.err; ok $?
     python -c "import json; d=json.load(open('$OUT/${n}_$rep.json')); print('$n', d['ms_per_step'], d['kernel_ms'])" || tail -5 $OUT/${n}_$rep.err
   done
 done

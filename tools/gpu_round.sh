@@ -15,10 +15,10 @@ for s in $STEPS; do
         || { tail -30 $OUT/pytest.log; exit 1; }
       tail -1 $OUT/pytest.log ;;
     bench)
-      timeout -k 10 300 python bench.py > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
+      timeout -k 10 300 python bench.py --full > $OUT/bench.json 2> $OUT/bench.err || { tail -20 $OUT/bench.err; exit 1; }
       python -c "import json; d=json.load(open('$OUT/bench.json')); print(d['value'], d['ms_per_step'], d['kernel_ms'], d['roofline']['frac'])" ;;
     benchq)
-      timeout -k 10 200 python bench.py --no-cpu-baseline > $OUT/benchq.json 2> $OUT/benchq.err || { tail -20 $OUT/benchq.err; exit 1; }
+      timeout -k 10 200 python bench.py --full --no-cpu-baseline > $OUT/benchq.json 2> $OUT/benchq.err || { tail -20 $OUT/benchq.err; exit 1; }
       python -c "import json; d=json.load(open('$OUT/benchq.json')); print(d['value'], d['ms_per_step'], d['kernel_ms'], d['roofline']['frac'])" ;;
     prof)
       timeout -k 10 300 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run -- python bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/prof.log 2>&1 \
