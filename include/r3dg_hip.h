@@ -229,7 +229,16 @@ typedef struct r3dg_backward_outputs {
 } r3dg_backward_outputs;
 
 /* RasterizeGaussiansBackwardCUDA (rasterize_points.cu:183-275). Every output element is written
- * (no pre-zeroing needed). Deterministic: per-Gaussian sums have a fixed order. */
+ * (no pre-zeroing needed). With r3dg_options.bwd_reduce = R3DG_REDUCE_ROWS the per-Gaussian sums
+ * have a fixed order and the result is bitwise reproducible; the default R3DG_REDUCE_ATOMIC adds
+ * them with f32 atomics, so last bits depend on arrival order (as the reference's).
+ *
+ * Prepared sums: a forward with the default shaders and no post passes, under R3DG_REDUCE_ATOMIC,
+ * stores the zeroed per-Gaussian sums behind the geometry state it returns. The first backward on
+ * that state, at that address, consumes them; every other backward (a second one on the same
+ * state, a state from another kind of forward, other options) zeroes its own scratch. A caller
+ * that moves a geometry state to another address before the backward loses nothing but that
+ * saving: the call takes the memset path. */
 int r3dg_rasterize_gaussians_backward(const r3dg_raster_settings* settings, const r3dg_gaussians* g,
                                       const int* radii, const r3dg_backward_grads* grads, void* geom,
                                       void* binning, void* image, int num_rendered, int backward_geometry,

@@ -169,7 +169,7 @@ __global__ void __launch_bounds__(256) preprocess_kernel(PreprocessArgs a) {
     // the per-tile counters of the atomic binning (bin_atomic_kernel) start at zero
     if (a.tile_count)
         for (int i = idx; i < a.num_tiles; i += (int)(gridDim.x * 256)) a.tile_count[i] = 0u;
-    // the single-pass scan's status words and ticket (rasterizer.hip scan_touched_kernel) start at zero
+    // the single-pass scan's status words and ticket (scan_touched_kernel) start at zero
     if (a.scan_status)
         for (int i = idx; i < a.scan_words; i += (int)(gridDim.x * 256)) a.scan_status[i] = 0ull;
     if (a.work_hist)
@@ -835,6 +835,99 @@ hipError_t launch_tile_depth_sort(int T, const uint2* ranges, const uint32_t* or
     if (T <= 0) return hipSuccess;
     hipLaunchKernelGGL(tile_depth_sort_kernel, dim3(T), dim3(kSortBT), 0, st, T, ranges, order, pairs, point_list,
                        kA, vA, kB, min_n);
+    return hipGetLastError();
+}
+
+// Inclusive scan of tiles_touched -> point_offsets (rasterizer_impl.cu:255-257 cub::InclusiveSum) in
+// one pass, and num_rendered published by the last workgroup: replaces rocPRIM's scan (an init
+// kernel + the scan kernel) and a one-thread publish kernel -- three launches, 18 us at M1 (round 6),
+// for 8 MB of traffic. The count goes straight into the pinned host words (a D2H copy cost a blit
+// kernel plus the copy engine's hand-back: 4.5 us + a 5.6 us gap before the next kernel). Workgroup b
+// scans its kScanItems contiguous items in registers / LDS and publishes its aggregate, then its inclusive prefix, in status[b] (decoupled look-back: flag in
+// the top bits of one 64-bit word with the value, so one atomic load reads both). status[] is zeroed
+// by preprocess_kernel, which runs before on the same stream. The grid (<= P / 16384 workgroups, 62
+// at M1) is co-resident, so the look-back spins only while a predecessor is still summing.
+constexpr int kScanThreads = 1024, kScanIPT = 16, kScanItems = kScanThreads * kScanIPT;
+constexpr uint64_t kScanAggregate = 1ull << 62, kScanInclusive = 2ull << 62;
+int scan_blocks(size_t P) { return (int)std::max<size_t>(1, (P + kScanItems - 1) / kScanItems); }
+__global__ void __launch_bounds__(kScanThreads) scan_touched_kernel(const uint32_t* __restrict__ in,
+                                                                    uint32_t* __restrict__ out, int P,
+                                                                    uint64_t* status,
+                                                                    const uint32_t* __restrict__ flag,
+                                                                    uint32_t* host) {
+    __shared__ uint32_t s_wave[kScanThreads / 64];
+    __shared__ uint32_t s_prefix;
+    __shared__ int s_b;
+    const int t = threadIdx.x, l = t & 63, w = t >> 6;
+    // the logical workgroup id from a ticket (status[gridDim.x], zeroed with the status words): a
+    // workgroup only ever waits for tickets drawn before its own, i.e. for running workgroups
+    if (t == 0) s_b = (int)__hip_atomic_fetch_add(status + gridDim.x, 1ull, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    __syncthreads();
+    const int b = s_b;
+    const int i0 = b * kScanItems + t * kScanIPT;
+    uint32_t v[kScanIPT];
+    if (i0 + kScanIPT <= P) {
+        const uint4* src = reinterpret_cast<const uint4*>(in + i0);  // in: 256-B aligned, i0 % 16 == 0
+#pragma unroll
+        for (int k = 0; k < kScanIPT / 4; ++k) {
+            const uint4 q = src[k];
+            v[4 * k] = q.x; v[4 * k + 1] = q.y; v[4 * k + 2] = q.z; v[4 * k + 3] = q.w;
+        }
+    } else {
+#pragma unroll
+        for (int k = 0; k < kScanIPT; ++k) v[k] = i0 + k < P ? in[i0 + k] : 0u;
+    }
+#pragma unroll
+    for (int k = 1; k < kScanIPT; ++k) v[k] += v[k - 1];
+    // exclusive scan of the thread totals across the workgroup
+    uint32_t x = v[kScanIPT - 1];
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const uint32_t y = __shfl_up(x, o);
+        if (l >= o) x += y;
+    }
+    if (l == 63) s_wave[w] = x;
+    __syncthreads();
+    uint32_t wpre = 0, agg = 0;
+#pragma unroll
+    for (int k = 0; k < kScanThreads / 64; ++k) {
+        const uint32_t s = s_wave[k];
+        wpre += k < w ? s : 0u;
+        agg += s;
+    }
+    const uint32_t texcl = wpre + x - v[kScanIPT - 1];
+    if (w == 0) {
+        if (b > 0 && l == 0)
+            __hip_atomic_store(status + b, kScanAggregate | agg, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+        const uint32_t prefix = lookback_prefix(status, b);
+        if (l == 0) {
+            __hip_atomic_store(status + b, kScanInclusive | (prefix + agg), __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_AGENT);
+            s_prefix = prefix;
+            if (b == (int)gridDim.x - 1) {  // the total: num_rendered into the pinned host words
+                if (flag) host[1] = *flag;
+                __threadfence_system();  // the flag before the count the host polls for
+                host[0] = prefix + agg;
+                __threadfence_system();
+            }
+        }
+    }
+    __syncthreads();
+    const uint32_t base = s_prefix + texcl;
+    if (i0 + kScanIPT <= P) {
+        uint4* dst = reinterpret_cast<uint4*>(out + i0);
+#pragma unroll
+        for (int k = 0; k < kScanIPT / 4; ++k)
+            dst[k] = make_uint4(base + v[4 * k], base + v[4 * k + 1], base + v[4 * k + 2], base + v[4 * k + 3]);
+    } else {
+#pragma unroll
+        for (int k = 0; k < kScanIPT; ++k)
+            if (i0 + k < P) out[i0 + k] = base + v[k];
+    }
+}
+hipError_t launch_scan_touched(const uint32_t* in, uint32_t* out, int P, uint64_t* status, const uint32_t* flag,
+                               uint32_t* host, hipStream_t st) {
+    hipLaunchKernelGGL(scan_touched_kernel, dim3(scan_blocks((size_t)P)), dim3(kScanThreads), 0, st, in, out, P,
+                       status, flag, host);
     return hipGetLastError();
 }
 

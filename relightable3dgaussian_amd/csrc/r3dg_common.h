@@ -491,7 +491,7 @@ __device__ __forceinline__ void half_live(float2 xy, float4 staged, float xa, fl
 }  // namespace r3dg
 
 namespace r3dg {
-// Decoupled look-back by one wave (single-pass scans, rasterizer.hip scan_touched_kernel /
+// Decoupled look-back by one wave (single-pass scans, preprocess.hip scan_touched_kernel /
 // preprocess.hip bin_colscan_kernel): the exclusive prefix of workgroup b from the 64-bit status
 // words of its predecessors ([flag: 62-63 | value: 0-31], flag 1 = the workgroup's aggregate, 2 = its
 // inclusive prefix, 0 = not published yet). Lane k polls predecessor b - 1 - k, so a window of 64

@@ -250,6 +250,11 @@ struct IntermediateArgs {
 // kernels (defined in the .hip translation units)
 __global__ void preprocess_kernel(PreprocessArgs a);
 __global__ void mark_visible_kernel(int P, const float* means3D, const float* view, uint8_t* present);
+// single-pass inclusive scan of tiles_touched; the last workgroup publishes the total (and the
+// prefiltered error flag, if any) in the pinned host words. status: scan_blocks(P) + 1 zeroed words
+int scan_blocks(size_t P);
+hipError_t launch_scan_touched(const uint32_t* in, uint32_t* out, int P, uint64_t* status, const uint32_t* flag,
+                               uint32_t* host, hipStream_t st);
 // counts, tile ranges, the longest-first tile order and every workgroup's scatter positions
 hipError_t launch_bin_prepare(const BinArgs& a, uint2* ranges, uint32_t* order, hipStream_t st);
 hipError_t launch_bin_scatter(const BinArgs& a, uint2* ranges, uint32_t* order, hipStream_t st);

@@ -21,7 +21,7 @@
 //   2. row_sum_kernel: one 8-lane group per Gaussian sums its flagged partial rows (contiguous:
 //      slots are Gaussian-major, duplicateWithKeys order) in a fixed order and expands the
 //      quadrant-centred moments -- bitwise reproducible run to run.
-//      render_bwd_dpp_kernel (R3DG_BWD=dpp) is the DPP-reduction cross-check writing the same rows.
+//      render_bwd_dpp_kernel (r3dg_options.test_bwd_dpp) is the DPP-reduction cross-check writing the same rows.
 //   3. gather_bwd_kernel: one thread per Gaussian expands the sums into the mean2D / conic / opacity
 //      gradients and runs the cov2D / projection / SH / cov3D backward.
 #include "r3dg_common.h"
@@ -87,7 +87,7 @@ __device__ __forceinline__ int block_max_last(int wmax, int* s_max_last) {
 // reductions (the atomic flush and row_sum_kernel) evaluate and sum it in double: for a mean ~1e3
 // px from its pixels the terms are ~1e6 times the result.
 
-// DPP variant (cross-check of the MFMA default, R3DG_BWD=dpp): the reference's per-channel
+// DPP variant (cross-check of the MFMA default, r3dg_options.test_bwd_dpp): the reference's per-channel
 // recurrences (backward.cu:544-579) step by step; every wave reduces its 64 pixels' values of an
 // instance with DPP and lane 63 writes the wave's partial row.
 template <int SMAX>

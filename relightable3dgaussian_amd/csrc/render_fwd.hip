@@ -400,7 +400,7 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
         a.bwd_rank[tile] = atomicAdd(a.bwd_hist + work_bucket(work), 1u);
     }
     // the backward's atomic sums (RenderFwdArgs::zero_sums): this tile's share, after its blend
-    if (!SHADER && a.zero_sums) {  // (training forwards only: never with splat shaders)
+    if (!SHADER && a.zero_sums) {  // (any atomic-mode forward without shaders or post passes)
         const uint32_t z0 = (uint32_t)tile * a.zero_chunk, z1 = min(z0 + a.zero_chunk, a.zero_n4);
         for (uint32_t i = z0 + (uint32_t)t; i < z1; i += kBlock) a.zero_sums[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }

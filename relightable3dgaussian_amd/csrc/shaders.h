@@ -2,7 +2,7 @@
 //
 // Restates the reference's shader library (cuda_rasterizer/ShShader.cu:62-190,
 // splatShader.cu:67-269, utils/shaderUtils.cu) and texture objects (utils/texture.cu:86-262).
-// Shaders are selected by registry id (rasterizer.hip shader_names), not device function
+// Shaders are selected by registry id (shaders.hip shader_names), not device function
 // pointers: every non-empty per-shader bucket of a shader manager launches the kernel
 // instantiated for that shader. Textures are float4 texel arrays in HBM sampled in software with
 // the CUDA texture-unit rules the reference relies on (normalized coordinates, wrap / clamp /
@@ -11,6 +11,7 @@
 #pragma once
 #include <map>
 #include <string>
+#include <vector>
 
 #include "r3dg_common.h"
 
@@ -73,7 +74,7 @@ __host__ __device__ inline float4 tex_sample(const TexDesc& t, float x, float y)
                        w00 * t00.w + w10 * t10.w + w01 * t01.w + w11 * t11.w);
 }
 
-// Registry ids (alphabetical, rasterizer.hip shader_names)
+// Registry ids (alphabetical, shaders.hip shader_names)
 enum ShShaderId { kShCullHalf = 0, kShExpPos = 1, kShGaussDissolve = 2, kShHeartbeat = 3, kShDefault = 4 };
 enum SplatShaderId {
     kSpCrack = 0, kSpCrackNoRecon = 1, kSpDissolve = 2, kSpNaiveOutline = 3, kSpQuantizeFlats = 4,
@@ -159,5 +160,25 @@ bool splat_shader_needs_features(int id);
 // texture manager registry (shaders.hip): name -> texture, plus the error texture
 bool lookup_texture_manager(int64_t handle, const std::map<std::string, TexDesc>** names, TexDesc* error);
 int texture_mode_channels(int mode);
+
+// shader registry and managers (shaders.hip). A handle is (kind + 1) << 32 | registry id.
+const std::vector<std::string>& shader_names(int kind);  // name order; empty for an unknown kind
+int handle_kind(int64_t h);
+int handle_index(int64_t h);
+struct ShaderManagerObj {
+    int kind;
+    std::vector<int> counts;       // per shader (name order)
+    std::vector<int*> d_lists;     // device splat-index list per shader
+    bool all_default;
+};
+const ShaderManagerObj* lookup_manager(int64_t h);  // null: handle 0 or unknown
+
+// The host's small per-Gaussian passes around the shaders; the caller checks the launches.
+// InitializeStencil (rasterizer_impl.cu:203-209)
+void launch_init_stencil(int P, float* stencil, float* stencil_opacity, hipStream_t st);
+// after the splat shaders: the records' opacity from conic_opacity.w, then the shader record
+// [shader colour, 0 | features, zero padded] (rec4 - 2 float4) of every visible Gaussian
+void launch_shader_records(int P, int S, int rec4, const int* radii, const float4* conic_opacity, float4* records,
+                           const float* shader_rgb, const float* feats, float4* shader_rec, hipStream_t st);
 
 }  // namespace r3dg

@@ -1,4 +1,5 @@
-// shaders.hip -- SH / splat shader library, texture objects and texture manager (gfx950).
+// shaders.hip -- SH / splat shader library, shader registry and managers, texture objects and
+// texture manager (gfx950).
 //
 // Restates cuda_rasterizer/ShShader.cu:62-190 (SH shaders: run before preprocessing on working
 // copies of positions / scales / rotations / opacity / SH), splatShader.cu:67-269 (splat
@@ -8,6 +9,8 @@
 // promotions (M_PI, 0.125, 1.5, M_1_PI literals) are kept.
 #pragma clang fp contract(off)
 
+#include <algorithm>
+#include <cstring>
 #include <map>
 #include <mutex>
 #include <string>
@@ -538,6 +541,151 @@ bool lookup_texture_manager(int64_t h, const std::map<std::string, TexDesc>** na
     return true;
 }
 
+// InitializeStencil (rasterizer_impl.cu:203-209)
+__global__ void __launch_bounds__(256) init_stencil_kernel(int P, float* stencil, float* stencil_opacity) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    stencil[i] = 0.0f;
+    stencil_opacity[i] = 1.0f;
+}
+
+// Splat shaders edit conic_opacity.w after the render records were written: refresh the records'
+// opacity (the backward reads records; the reference's backward reads the edited geometry state).
+__global__ void __launch_bounds__(256) refresh_record_opacity_kernel(int P, const int* __restrict__ radii,
+                                                                     const float4* __restrict__ conic_opacity,
+                                                                     float4* __restrict__ records, int rec4) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P || radii[i] <= 0) return;
+    records[(size_t)i * rec4].w = conic_opacity[i].w;
+}
+
+// The shader record of every visible Gaussian (render_fwd_glds_kernel<SMAX, true>): na4 float4 in
+// the attribute row's layout, [shader colour, 0 | the splat shaders' features, zero padded] -- the
+// blend's staged colour and feature columns after the splat shaders ran. One thread per float4, so
+// the stores are coalesced (a thread per Gaussian wrote a 112-byte row each: 0.37 ms at 1 M, S = 21).
+__global__ void __launch_bounds__(256) shader_record_kernel(int P, int na4, const int* __restrict__ radii,
+                                                            const float* __restrict__ shader_rgb,
+                                                            const float* __restrict__ feats, int S,
+                                                            float4* __restrict__ shader_rec) {
+    const long long e = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (e >= (long long)P * na4) return;
+    const int i = (int)(e / na4), q = (int)(e - (long long)i * na4);
+    if (radii[i] <= 0) return;
+    float v[4];
+    if (q == 0) {
+        v[0] = shader_rgb[3 * i]; v[1] = shader_rgb[3 * i + 1]; v[2] = shader_rgb[3 * i + 2]; v[3] = 0.f;
+    } else {
+#pragma unroll
+        for (int k = 0; k < 4; ++k) {
+            const int c = 4 * (q - 1) + k;
+            v[k] = c < S ? feats[(size_t)i * S + c] : 0.f;
+        }
+    }
+    shader_rec[e] = make_float4(v[0], v[1], v[2], v[3]);
+}
+
+void launch_init_stencil(int P, float* stencil, float* stencil_opacity, hipStream_t st) {
+    hipLaunchKernelGGL(init_stencil_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, stencil, stencil_opacity);
+}
+void launch_shader_records(int P, int S, int rec4, const int* radii, const float4* conic_opacity, float4* records,
+                           const float* shader_rgb, const float* feats, float4* shader_rec, hipStream_t st) {
+    hipLaunchKernelGGL(refresh_record_opacity_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, radii,
+                       conic_opacity, records, rec4);
+    const int na4 = rec4 - 2;
+    hipLaunchKernelGGL(shader_record_kernel, dim3((unsigned)(((long long)P * na4 + 255) / 256)), dim3(256), 0, st,
+                       P, na4, radii, shader_rgb, feats, S, shader_rec);
+}
+
+// ---- shader registry (ShShader.cu:196-230, splatShader.cu:283-333, postProcessShader.cu:395-436) ----
+// Handles are opaque ids: (kind + 1) << 32 | index into the alphabetically ordered name list
+// (the reference's ShaderManager iterates a std::map, i.e. in name order).
+const std::vector<std::string>& shader_names(int kind) {
+    static const std::vector<std::string> sh = {"CullHalf", "ExpPos", "GaussDissolve", "Heartbeat", "ShDefault"};
+    static const std::vector<std::string> splat = {"Crack",         "CrackNoRecon",  "Dissolve",     "NaiveOutline",
+                                                   "QuantizeFlats", "QuantizeLight", "RoughnessOnly", "SplatDefault",
+                                                   "Stencil",       "Wireframe"};
+    static const std::vector<std::string> post = {"BlurLighting", "CrackReconstriction", "Invert",
+                                                  "Outline",      "QuantizeLighting",    "SobelFilter",
+                                                  "SplatDefault", "TexturedShadows",     "ToonShader"};
+    static const std::vector<std::string> none;
+    return kind == R3DG_SHADER_SH ? sh : kind == R3DG_SHADER_SPLAT ? splat : kind == R3DG_SHADER_POST ? post : none;
+}
+static int64_t make_handle(int kind, int idx) { return ((int64_t)(kind + 1) << 32) | (int64_t)idx; }
+int handle_kind(int64_t h) { return (int)(h >> 32) - 1; }
+int handle_index(int64_t h) { return (int)(h & 0xffffffff); }
+static int default_index(int kind) {
+    const auto& n = shader_names(kind);
+    const char* d = kind == R3DG_SHADER_SH ? "ShDefault" : "SplatDefault";
+    return (int)(std::find(n.begin(), n.end(), d) - n.begin());
+}
+
+static std::mutex g_mgr_mu;
+static std::map<int64_t, ShaderManagerObj*> g_managers;
+static int64_t g_next_mgr = 1;
+
+const ShaderManagerObj* lookup_manager(int64_t h) {
+    if (h == 0) return nullptr;
+    std::lock_guard<std::mutex> lk(g_mgr_mu);
+    auto it = g_managers.find(h);
+    return it == g_managers.end() ? nullptr : it->second;
+}
+
+static int build_manager(int kind, int P, const std::vector<int>& idx_per_splat, int64_t* out, hipStream_t st) {
+    const int n = (int)shader_names(kind).size();
+    auto* m = new ShaderManagerObj();
+    m->kind = kind;
+    m->counts.assign(n, 0);
+    std::vector<std::vector<int>> lists(n);
+    for (int i = 0; i < P; ++i) {
+        const int s = idx_per_splat[i];
+        if (s < 0 || s >= n) {
+            delete m;
+            set_error("shader manager: invalid shader index");
+            return R3DG_ERR_ARG;
+        }
+        lists[s].push_back(i);  // ascending splat order, as SortShadersCUDA (preprocessModel.cu:116-134)
+    }
+    m->all_default = true;
+    for (int s = 0; s < n; ++s) {
+        m->counts[s] = (int)lists[s].size();
+        int* d = nullptr;
+        if (!lists[s].empty()) {
+            R3DG_CHECK_HIP(hipMalloc(&d, sizeof(int) * lists[s].size()));
+            R3DG_CHECK_HIP(hipMemcpyAsync(d, lists[s].data(), sizeof(int) * lists[s].size(), hipMemcpyHostToDevice, st));
+            if (s != default_index(kind)) m->all_default = false;
+        }
+        m->d_lists.push_back(d);
+    }
+    R3DG_CHECK_HIP(hipStreamSynchronize(st));
+    std::lock_guard<std::mutex> lk(g_mgr_mu);
+    const int64_t h = (int64_t)0x5233000000000000ll | g_next_mgr++;
+    g_managers[h] = m;
+    *out = h;
+    return R3DG_OK;
+}
+
+// preprocessModel.cu:17-59 (SelectShadersCUDA): shader choice by splat position.
+__global__ void select_shaders_kernel(int P, const float* __restrict__ xyz, int8_t* sh_idx, int8_t* splat_idx,
+                                      int i_sh_default, int i_heartbeat, int i_gauss_dissolve, int i_splat_default,
+                                      int i_wireframe, int i_outline, int i_dissolve) {
+    const int i = blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= P) return;
+    const float x = xyz[3 * i], y = xyz[3 * i + 1];
+    sh_idx[i] = (int8_t)(y < -0.3f ? i_sh_default : (y > 0.4f ? i_heartbeat : i_gauss_dissolve));
+    int s;
+    if (x < -0.6f) s = i_splat_default;
+    else if (x > -0.6f && x < 0) s = i_wireframe;
+    else if (x > 0 && x < 0.5) s = i_outline;
+    else s = i_dissolve;
+    splat_idx[i] = (int8_t)s;
+}
+
+static int name_index(int kind, const char* name) {
+    const auto& n = shader_names(kind);
+    auto it = std::find(n.begin(), n.end(), std::string(name));
+    return it == n.end() ? -1 : (int)(it - n.begin());
+}
+
 }  // namespace r3dg
 
 using namespace r3dg;
@@ -587,4 +735,81 @@ extern "C" int r3dg_texture_manager_create(int n, const char* const* names, cons
     g_tex_managers[h] = m;
     *manager = h;
     return R3DG_OK;
+}
+
+extern "C" int r3dg_shader_count(int kind) { return (int)shader_names(kind).size(); }
+extern "C" const char* r3dg_shader_name(int kind, int index) {
+    const auto& n = shader_names(kind);
+    return (index >= 0 && index < (int)n.size()) ? n[index].c_str() : nullptr;
+}
+extern "C" int64_t r3dg_shader_handle(int kind, int index) {
+    const auto& n = shader_names(kind);
+    return (index >= 0 && index < (int)n.size()) ? make_handle(kind, index) : 0;
+}
+
+extern "C" int r3dg_preprocess_model(int P, const float* xyz, int64_t* sh_manager, int64_t* splat_manager,
+                                     r3dg_stream_t stream) {
+    hipStream_t st = (hipStream_t)stream;
+    R3DG_REQUIRE(P >= 0 && sh_manager && splat_manager, "PreprocessModel: invalid arguments");
+    std::vector<int8_t> hs(P), hp(P);
+    if (P > 0) {
+        int8_t *ds = nullptr, *dp = nullptr;
+        R3DG_CHECK_HIP(hipMalloc(&ds, P));
+        R3DG_CHECK_HIP(hipMalloc(&dp, P));
+        hipLaunchKernelGGL(select_shaders_kernel, dim3((P + 255) / 256), dim3(256), 0, st, P, xyz, ds, dp,
+                           name_index(R3DG_SHADER_SH, "ShDefault"), name_index(R3DG_SHADER_SH, "Heartbeat"),
+                           name_index(R3DG_SHADER_SH, "GaussDissolve"), name_index(R3DG_SHADER_SPLAT, "SplatDefault"),
+                           name_index(R3DG_SHADER_SPLAT, "Wireframe"), name_index(R3DG_SHADER_SPLAT, "NaiveOutline"),
+                           name_index(R3DG_SHADER_SPLAT, "Dissolve"));
+        R3DG_CHECK_HIP(hipGetLastError());
+        R3DG_CHECK_HIP(hipMemcpyAsync(hs.data(), ds, P, hipMemcpyDeviceToHost, st));
+        R3DG_CHECK_HIP(hipMemcpyAsync(hp.data(), dp, P, hipMemcpyDeviceToHost, st));
+        R3DG_CHECK_HIP(hipStreamSynchronize(st));
+        R3DG_CHECK_HIP(hipFree(ds));
+        R3DG_CHECK_HIP(hipFree(dp));
+    }
+    std::vector<int> is(hs.begin(), hs.end()), ip(hp.begin(), hp.end());
+    int rc = build_manager(R3DG_SHADER_SH, P, is, sh_manager, st);
+    if (rc) return rc;
+    return build_manager(R3DG_SHADER_SPLAT, P, ip, splat_manager, st);
+}
+
+extern "C" int r3dg_create_shader_manager(int kind, int P, const int64_t* handles, int64_t* manager,
+                                          r3dg_stream_t stream) {
+    R3DG_REQUIRE(kind == R3DG_SHADER_SH || kind == R3DG_SHADER_SPLAT, "create_shader_manager: bad kind");
+    R3DG_REQUIRE(P >= 0 && manager && (P == 0 || handles), "create_shader_manager: invalid arguments");
+    std::vector<int> idx(P);
+    for (int i = 0; i < P; ++i) {
+        R3DG_REQUIRE(handle_kind(handles[i]) == kind, "create_shader_manager: handle of the wrong shader kind");
+        idx[i] = handle_index(handles[i]);
+    }
+    return build_manager(kind, P, idx, manager, (hipStream_t)stream);
+}
+
+extern "C" int r3dg_shader_manager_info(int64_t manager, int* n_shaders, int64_t* handles, int* counts) {
+    const ShaderManagerObj* m = lookup_manager(manager);
+    R3DG_REQUIRE(m, "shader_manager_info: unknown handle");
+    const int n = (int)m->counts.size();
+    if (n_shaders) *n_shaders = n;
+    for (int i = 0; i < n; ++i) {
+        if (handles) handles[i] = make_handle(m->kind, i);
+        if (counts) counts[i] = m->counts[i];
+    }
+    return R3DG_OK;
+}
+
+// utils/texture.cu:33-76
+extern "C" int r3dg_encode_texture_mode(const char* mode) {
+    static const char* names[] = {"1", "L", "P", "RGB", "RGBA", "CMYK", "YCbCr", "LAB", "HSV", "I", "F"};
+    for (int i = 0; i < 11; ++i)
+        if (mode && strcmp(mode, names[i]) == 0) return i;
+    return -1;
+}
+extern "C" int r3dg_encode_wrap_mode(const char* mode) {
+    if (!mode) return -1;
+    if (!strcmp(mode, "Border")) return (int)hipAddressModeBorder;
+    if (!strcmp(mode, "Clamp")) return (int)hipAddressModeClamp;
+    if (!strcmp(mode, "Mirror")) return (int)hipAddressModeMirror;
+    if (!strcmp(mode, "Wrap")) return (int)hipAddressModeWrap;
+    return -1;
 }
