@@ -477,6 +477,24 @@ int r3dg_bvh_trace(int num_rays, int num_gaussians, const int32_t* nodes, const 
                    void* alloc_ctx, int* num_rendered, int32_t** point_list, float** position_list,
                    int32_t** ray_id_list, r3dg_stream_t stream);
 
+/* ---- nearest-neighbour distances (reference module simple_knn._C) --------------------------- */
+
+/* distCUDA2 (submodules/simple-knn/spatial.cu:15-26, simple_knn.cu:185-221): mean squared distance
+ * of every point to its three nearest other points, mean_dist2[i] = ((b0 + b1) + b2) / 3.0f with
+ * b0 <= b1 <= b2 the three smallest d2(i, j) over j != i, d2 = (dx*dx + dy*dy) + dz*dz, d = p_j - p_i,
+ * all in f32 without FMA contraction and an IEEE division. Exclusion is by index: a duplicate point
+ * at distance 0 counts. A missing neighbour is FLT_MAX (P = 1, 2: +inf; P = 3: about FLT_MAX / 3).
+ * The search is exact (boxes are pruned on a lower bound of d2 only), so the result is that of a
+ * brute force and does not depend on the internal ordering. Inputs are expected finite; with NaN /
+ * Inf coordinates the values are unspecified, but the call terminates and stays in bounds.
+ * points f32 [P, 3], mean_dist2 f32 [P]. P < 0, a NULL points / mean_dist2 / scratch_alloc with
+ * P > 0: R3DG_ERR_ARG; P == 0: R3DG_OK, nothing launched. Everything is enqueued on stream, with no
+ * host synchronisation. Scratch from scratch_alloc: 32 B per point (two (code, index) pairs and the
+ * Morton-ordered float4 copy), 32 B per 64 points (box bounds) and per 4096 points (super-box
+ * bounds), and the radix sort's workspace. */
+int r3dg_knn_mean_dist2(int P, const float* points /* [P,3] */, float* mean_dist2 /* [P] */,
+                        r3dg_alloc_fn scratch_alloc, void* scratch_ctx, r3dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -8,7 +8,9 @@ requires GPU tensors.
 `install_alias()` registers this package as `r3dg_rasterization` so the reference's
 `from r3dg_rasterization import _C` (gaussian_renderer/r3dg_rasterization.py:7-8,
 scene/gaussian_model.py:18) resolves here, and `relightable3dgaussian_amd.bvh` as the reference's
-`bvh` package (`from bvh import RayTracer`, scene/gaussian_model.py:16) (INTEGRATION.md).
+`bvh` package (`from bvh import RayTracer`, scene/gaussian_model.py:16) and
+`relightable3dgaussian_amd.simple_knn` as its `simple_knn` extension (`from simple_knn._C import
+distCUDA2`, scene/gaussian_model.py:13) (INTEGRATION.md).
 """
 from __future__ import annotations
 
@@ -51,6 +53,10 @@ def install_alias() -> None:
     from .bvh import install_bvh_alias
 
     install_bvh_alias()
+    # the reference's nearest-neighbour extension simple_knn._C (scene/gaussian_model.py:13)
+    from .simple_knn import install_simple_knn_alias
+
+    install_simple_knn_alias()
 
 
 __all__ = ["_C", "install_alias", "HIP_LIB", "EXT_LIB"]

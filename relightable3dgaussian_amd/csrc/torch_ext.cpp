@@ -806,6 +806,24 @@ std::tuple<torch::Tensor, torch::Tensor, torch::Tensor> create_bvh(const torch::
     return {nodes, aabbs, morton};
 }
 
+// distCUDA2 (submodules/simple-knn/spatial.cu:15-26): [P,3] f32 points -> [P] mean squared distance to
+// the three nearest other points, on the current stream
+torch::Tensor dist_cuda2(const torch::Tensor& points) {
+    TORCH_CHECK(points.scalar_type() == torch::kFloat32, "distCUDA2: expected float32");
+    TORCH_CHECK(points.dim() == 2 && points.size(1) == 3, "distCUDA2: points [P,3] expected");
+    TORCH_CHECK(points.is_cuda(), "distCUDA2: expected a GPU tensor (this build has no CPU path)");
+    TORCH_CHECK(points.size(0) < (int64_t(1) << 30), "distCUDA2: too many points");
+    const auto p = points.contiguous();
+    const int64_t P = p.size(0);
+    const c10::OptionalDeviceGuard guard(p.device());
+    auto out = torch::empty({P}, p.options());
+    TensorAlloc scratch{p.options().dtype(torch::kUInt8), {}};
+    check(r3dg_knn_mean_dist2((int)P, P ? p.data_ptr<float>() : nullptr, P ? out.data_ptr<float>() : nullptr,
+                              tensor_alloc, &scratch, stream_of(p.device())),
+          "distCUDA2");
+    return out;
+}
+
 // trace_bvh_opacity (bvh/src/bvh.cu:87-117): outputs shaped like rays_o without its last axis
 std::tuple<torch::Tensor, torch::Tensor> trace_bvh_opacity(const torch::Tensor& nodes, const torch::Tensor& aabbs,
                                                            const torch::Tensor& rays_o, const torch::Tensor& rays_d,
@@ -959,6 +977,8 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("trace_bvh", &trace_bvh);
     m.def("trace_bvh_opacity", &trace_bvh_opacity);
     m.def("bvh_leaf_aabbs", &bvh_leaf_aabbs);
+    // nearest-neighbour distances: the reference's simple_knn._C (submodules/simple-knn/ext.cpp)
+    m.def("distCUDA2", &dist_cuda2);
     m.def("profile_enable", [](int64_t n) { check(r3dg_profile_enable((int)n), "profile_enable"); });
     m.def("profile_read", [](int64_t kernel) {
         int c = 0;

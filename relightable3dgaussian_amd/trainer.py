@@ -81,6 +81,7 @@ class GaussianTrainState:
     dist: _Dist = field(default_factory=_Dist)
     betas: tuple = (0.9, 0.999)
     eps: float = 1e-15                 # gaussian_model.py:613
+    spatial_lr_scale: float = 1.0      # gaussian_model.py:538 (create_from_pcd), read by training_setup
 
     # ---- construction ------------------------------------------------------------------------
     @staticmethod
@@ -175,6 +176,41 @@ class GaussianTrainState:
         return GaussianTrainState.from_tensors({k: torch.from_numpy(v).to(device) for k, v in arrs.items()},
                                                use_pbr=use_pbr, **kw)
 
+    @staticmethod
+    def create_from_pcd(points, colors, normals, spatial_lr_scale: float = 1.0, use_pbr: bool = True,
+                        max_sh_degree: int = 3, device="cuda", **kw):
+        """create_from_pcd (gaussian_model.py:537-580) straight into the flat parameter buffer: the
+        point cloud's positions and normals, colours as the SH DC term, isotropic scales from the mean
+        squared distance to the three nearest neighbours (`_C.distCUDA2`), identity rotations, opacity
+        0.1 and zero PBR groups. points / colors / normals: [P, 3] numpy arrays or torch tensors."""
+        import torch
+
+        from . import _C
+
+        if max_sh_degree != 3:
+            raise ValueError("create_from_pcd: the flat parameter layout holds SH degree 3 (f_rest [P,15,3])")
+
+        def dev(a):
+            return torch.as_tensor(a).float().to(device)
+
+        xyz, normal, color = dev(points), dev(normals), dev(colors)
+        P = xyz.shape[0]
+        n_rest = (max_sh_degree + 1) ** 2 - 1
+        dist2 = torch.clamp_min(_C.distCUDA2(xyz), 0.0000001)
+        rots = torch.zeros((P, 4), device=xyz.device)
+        rots[:, 0] = 1
+        opac = 0.1 * torch.ones((P, 1), dtype=torch.float, device=xyz.device)
+        t = {"xyz": xyz, "normal": normal, "rotation": rots,
+             "scaling": torch.log(torch.sqrt(dist2))[..., None].repeat(1, 3),
+             "opacity": torch.log(opac / (1 - opac)),  # inverse_sigmoid (utils/general_utils.py:19-20)
+             "f_dc": ((color - 0.5) / 0.28209479177387814)[:, None, :],  # RGB2SH (utils/sh_utils.py:114-115)
+             "f_rest": torch.zeros((P, n_rest, 3), device=xyz.device)}
+        if use_pbr:
+            t.update({n: torch.zeros((P, *s), device=xyz.device) for n, s in PBR_GROUPS})
+        st = GaussianTrainState.from_tensors(t, use_pbr=use_pbr, **kw)
+        st.spatial_lr_scale = float(spatial_lr_scale)
+        return st
+
     def save_ply(self, path: str) -> None:
         """save_ply (gaussian_model.py:658-686) from the flat parameter buffer."""
         from .ply import save_ply
@@ -183,8 +219,11 @@ class GaussianTrainState:
         save_ply(path, {n: self.view(n) for n in names}, use_pbr="base_color" in names)
 
     # ---- gaussian_model.py:581-620 -------------------------------------------------------------
-    def training_setup(self, training_args, spatial_lr_scale=1.0):
+    def training_setup(self, training_args, spatial_lr_scale=None):
+        """spatial_lr_scale: None takes the state's own (1.0 unless create_from_pcd stored another)."""
         a = training_args
+        if spatial_lr_scale is None:
+            spatial_lr_scale = self.spatial_lr_scale
         self.percent_dense = a.percent_dense
         self._reset_stats()
         lr = {"xyz": a.position_lr_init * spatial_lr_scale, "normal": a.normal_lr, "rotation": a.rotation_lr,
