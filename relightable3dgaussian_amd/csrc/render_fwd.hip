@@ -71,7 +71,12 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
     static_assert(NB == 64, "one 64-bit contribution word per wave and batch");
     // one LDS array: [2 staging buffers | 2 x 64 x 4 contribution flags (batch buffer, instance, wave)
     // | the tile's sorted Gaussian ids (fused sort)]; the fused sort's scratch aliases the staging
-    constexpr int SORT4 = (int)((sizeof(TileSortLds<kFusedSortMax / kSortBT>) + 15) / 16);
+#if R3DG_FWD_SORT_BUCKET
+    using FusedSortLds = TileBucketSortLds<kFusedSortMax / kSortBT>;  // bucket sort | its radix fallback
+#else
+    using FusedSortLds = TileSortLds<kFusedSortMax / kSortBT>;
+#endif
+    constexpr int SORT4 = (int)((sizeof(FusedSortLds) + 15) / 16);
     constexpr int STG = 2 * SBUF > SORT4 ? 2 * SBUF : SORT4;  // float4 of staging / sort scratch
     __shared__ float4 s_lds[STG + 64 + kFusedSortMax / 4];
     uint8_t* const s_cf = reinterpret_cast<uint8_t*>(s_lds + STG);
@@ -92,7 +97,9 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
 
     // fused depth sort (block-uniform): the tile's (depth bits, id) pairs sorted in the prologue
     // (r3dg_tilesort.h), ids kept in LDS for the staging and written out for the backward; saves
-    // the standalone sort launch, whose time is its barriers' latency, not its work
+    // the standalone sort launch. Here the sort's latency hides under the other resident workgroups
+    // and its instructions are what costs: a one-pass bucket sort (R3DG_FWD_SORT_BUCKET), 0.037 ms
+    // less of this kernel at M1 than the radix sort's passes
     const bool fused = a.pairs != nullptr && n <= kFusedSortMax;
     if (fused && n > 0) {
         constexpr int IPT = kFusedSortMax / kSortBT;
@@ -104,6 +111,17 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
             keys[k] = kv.x;
             vals[k] = kv.y;
         }
+#if R3DG_FWD_SORT_BUCKET && !defined(R3DG_EXP_NOSORT)
+        // the ids land in s_ids by final rank; the list for the backward is written from there,
+        // consecutive lanes on consecutive positions
+        sort_tile_bucket<IPT>(keys, vals, n, *reinterpret_cast<FusedSortLds*>(s_lds), s_ids);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < IPT; ++k) {
+            const int i = t + k * kSortBT;
+            if (i < n) a.point_list_out[range.x + i] = s_ids[i];
+        }
+#else
 #ifndef R3DG_EXP_NOSORT  // timing experiment only (results invalid): the blend without the fused sort
         if (n > 1) sort_pairs_chunk<IPT>(keys, vals, n, *reinterpret_cast<TileSortLds<IPT>*>(s_lds));
 #endif
@@ -116,6 +134,7 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
             }
         }
         __syncthreads();
+#endif
     }
 
 #if R3DG_FWD_TSIGN

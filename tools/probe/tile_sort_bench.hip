@@ -1,7 +1,11 @@
 // tile_sort_bench.hip -- variants of the per-tile depth sort (preprocess.hip tile_depth_sort_kernel)
 // on an M1-shaped synthetic input: 8160 tiles of ~614 instances (max < 1024), Gaussian ids
 // ascending within each tile, depth keys = float bits of U(3, 8). Median of 20 launches each.
-//   hipcc -O3 --offload-arch=gfx950 -std=c++17 tools/probe/tile_sort_bench.hip -o /tmp/tsb && /tmp/tsb
+// The forward blend's two fused sorts (r3dg_tilesort.h: sort_pairs_chunk, the rocPRIM chunk sort, and
+// sort_tile_bucket, the one-pass bucket sort) run on the same tiles, both checked against a host
+// std::sort by (key, id); the time of each per 8160 tiles is printed.
+//   hipcc -O3 --offload-arch=gfx950 -std=c++17 -Iinclude -Irelightable3dgaussian_amd/csrc \
+//       tools/probe/tile_sort_bench.hip -o tools/probe/bin/tile_sort_bench && tools/probe/bin/tile_sort_bench
 #include <cstring>
 #include <hip/hip_runtime.h>
 #include <rocprim/block/block_radix_sort.hpp>
@@ -10,6 +14,8 @@
 #include <cstdio>
 #include <random>
 #include <vector>
+
+#include "r3dg_tilesort.h"
 
 #define CK(x)                                                                   \
     do {                                                                        \
@@ -79,6 +85,45 @@ __global__ void __launch_bounds__(BS) sort_kernel(int T, const uint2* ranges, co
     }
 }
 
+// The forward's fused sorts as the blend calls them: BUCKET = 0 sort_pairs_chunk, 1 sort_tile_bucket.
+template <int BUCKET>
+__global__ void __launch_bounds__(r3dg::kSortBT) fused_sort_kernel(int T, const uint2* ranges, const uint32_t* depth_keys,
+                                                                  uint32_t* plist) {
+    constexpr int IPT = 4;
+    __shared__ float4 s_scratch[(sizeof(r3dg::TileBucketSortLds<IPT>) + 15) / 16];
+    __shared__ uint32_t s_ids[r3dg::kSortBT * IPT];
+    auto& lds = *reinterpret_cast<r3dg::TileBucketSortLds<IPT>*>(s_scratch);
+    const uint2 rg = ranges[blockIdx.x];
+    const uint32_t s = rg.x;
+    const int n = (int)(rg.y - rg.x), t = threadIdx.x;
+    if (n <= 0) return;
+    uint32_t keys[IPT], vals[IPT];
+#pragma unroll
+    for (int k = 0; k < IPT; ++k) {
+        const int i = t * IPT + k;
+        const uint32_t g = i < n ? plist[s + i] : 0xffffffffu;
+        vals[k] = g;
+        keys[k] = i < n ? depth_keys[g] : 0xffffffffu;
+    }
+    if constexpr (BUCKET) {
+        r3dg::sort_tile_bucket<IPT>(keys, vals, n, lds, s_ids);
+        __syncthreads();
+#pragma unroll
+        for (int k = 0; k < IPT; ++k) {
+            const int i = t + k * r3dg::kSortBT;
+            if (i < n) plist[s + i] = s_ids[i];
+        }
+    } else {
+        __syncthreads();  // (every load of the unsorted list before the sorted stores)
+        r3dg::sort_pairs_chunk<IPT>(keys, vals, n, lds.radix);
+#pragma unroll
+        for (int k = 0; k < IPT; ++k) {
+            const int i = t * IPT + k;
+            if (i < n) plist[s + i] = vals[k];
+        }
+    }
+}
+
 template <typename K>
 float timeit(const char* name, K kern, int T, const uint2* r, const uint32_t* dk, uint32_t* pl, const uint32_t* pl0,
              size_t L, int bs) {
@@ -112,6 +157,8 @@ int main() {
         std::vector<uint32_t> g(c);
         for (auto& x : g) x = rng() % P;
         std::sort(g.begin(), g.end());
+        g.erase(std::unique(g.begin(), g.end()), g.end());  // a Gaussian occurs once per tile
+        c = (int)g.size();
         ranges[t] = make_uint2((uint32_t)plist.size(), (uint32_t)(plist.size() + c));
         plist.insert(plist.end(), g.begin(), g.end());
     }
@@ -132,6 +179,21 @@ int main() {
     CK(hipMemcpy(ddk, dk.data(), 4 * P, hipMemcpyHostToDevice));
     CK(hipMemcpy(dpl0, plist.data(), 4 * L, hipMemcpyHostToDevice));
     printf("L = %zu\n", L);
+    {   // the forward's fused sorts against a host sort by (key, id)
+        std::vector<uint32_t> want(plist);
+        for (int t = 0; t < T; ++t)
+            std::sort(want.begin() + ranges[t].x, want.begin() + ranges[t].y, [&](uint32_t a, uint32_t b) {
+                return dk[a] < dk[b] || (dk[a] == dk[b] && a < b);
+            });
+        std::vector<uint32_t> got(L);
+        const float tr = timeit("fused: rocprim chunk sort (sort_pairs_chunk)", fused_sort_kernel<0>, T, dr, ddk, dpl, dpl0, L, 256);
+        CK(hipMemcpy(got.data(), dpl, 4 * L, hipMemcpyDeviceToHost));
+        printf("  == host std::sort by (key, id): %d\n", (int)(got == want));
+        const float tb = timeit("fused: bucket sort (sort_tile_bucket)", fused_sort_kernel<1>, T, dr, ddk, dpl, dpl0, L, 256);
+        CK(hipMemcpy(got.data(), dpl, 4 * L, hipMemcpyDeviceToHost));
+        printf("  == host std::sort by (key, id): %d\n", (int)(got == want));
+        printf("per %d tiles: rocprim chunk sort %.1f us, bucket sort %.1f us\n", T, tr * 1e3, tb * 1e3);
+    }
     timeit("floor (load+gather+store) 256x4", sort_kernel<256, 4, 0>, T, dr, ddk, dpl, dpl0, L, 256);
     timeit("rocprim 32b 256x4", sort_kernel<256, 4, 1>, T, dr, ddk, dpl, dpl0, L, 256);
     std::vector<uint32_t> ref(L);
