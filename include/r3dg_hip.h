@@ -495,6 +495,46 @@ int r3dg_bvh_trace(int num_rays, int num_gaussians, const int32_t* nodes, const 
 int r3dg_knn_mean_dist2(int P, const float* points /* [P,3] */, float* mean_dist2 /* [P] */,
                         r3dg_alloc_fn scratch_alloc, void* scratch_ctx, r3dg_stream_t stream);
 
+/* ---- image loss (reference: utils/loss_utils.py, utils/image_utils.py) ----------------------- */
+
+/* The L1 + SSIM loss of calculate_loss (gaussian_renderer/neilf.py:216-222) in fused form: ssim
+ * (utils/loss_utils.py:31-62: 11x11 Gaussian window of sigma 1.5, zero padding 5, C1 = 0.01^2,
+ * C2 = 0.03^2, all in f32), F.l1_loss and the squared error behind psnr (utils/image_utils.py:24-29).
+ *
+ * An image is `planes` (= batch * channels) independent [H, W] planes. Element (p, y, x) of img is
+ * img[p * img_plane_stride + y * img_row_stride + x * img_px_stride] (strides in elements), gt
+ * likewise: CHW is (H*W, W, 1), the rasterizer's HWC is (1, W*C, C).
+ *
+ * forward: sums f32 [planes, 3] = per plane the sums over its pixels of ssim_map, |img - gt| and
+ * (img - gt)^2 (divide by H*W for the means). Tile partials are added in a fixed order in f64, so the
+ * result is bitwise reproducible. dmaps: NULL (evaluation: nothing but sums is written) or f32
+ * [3, planes, H, W] receiving per pixel the derivatives of ssim_map by mu1, by the window mean of
+ * img^2 and by the window mean of img*gt, which the backward consumes. Scratch from scratch_alloc:
+ * 12 B per 16x16 tile.
+ *
+ * backward: dL_dimg (addressed with img's strides) =
+ *   scale[p] * (w_ssim[p] * d(sum of ssim_map over plane p)/d img + w_abs[p] * sign(img - gt)),
+ * sign(0) = 0 as F.l1_loss differentiates. w_ssim, w_abs f32 [planes] and the optional scale f32
+ * [planes] (NULL: 1) are device arrays; scale multiplies last, so a loss scaled by k gives
+ * fl(k * gradient) exactly. There is no gradient with respect to gt.
+ *
+ * Negative planes / H / W, planes*H*W > INT32_MAX, a NULL required pointer or a NULL scratch_alloc:
+ * R3DG_ERR_ARG before any device work. planes, H or W == 0: R3DG_OK, nothing launched or allocated.
+ * Everything is enqueued on stream, with no host synchronisation. */
+int r3dg_image_loss_forward(int planes, int H, int W, const float* img, int64_t img_plane_stride,
+                            int64_t img_row_stride, int64_t img_px_stride, const float* gt,
+                            int64_t gt_plane_stride, int64_t gt_row_stride, int64_t gt_px_stride,
+                            float* sums /* [planes,3] */, float* dmaps /* [3,planes,H,W] or NULL */,
+                            r3dg_alloc_fn scratch_alloc, void* scratch_ctx, r3dg_stream_t stream);
+int r3dg_image_loss_backward(int planes, int H, int W, const float* img, int64_t img_plane_stride,
+                             int64_t img_row_stride, int64_t img_px_stride, const float* gt,
+                             int64_t gt_plane_stride, int64_t gt_row_stride, int64_t gt_px_stride,
+                             const float* dmaps /* [3,planes,H,W] */, const float* w_ssim /* [planes] */,
+                             const float* w_abs /* [planes] */, const float* scale /* [planes] or NULL */,
+                             float* dL_dimg, r3dg_stream_t stream);
+/* the 11 window weights the kernels use: gaussian(11, 1.5) of utils/loss_utils.py:19-21 in f32 (host memory) */
+const float* r3dg_image_loss_window(void);
+
 #ifdef __cplusplus
 }
 #endif

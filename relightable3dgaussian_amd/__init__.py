@@ -11,6 +11,9 @@ scene/gaussian_model.py:18) resolves here, and `relightable3dgaussian_amd.bvh` a
 `bvh` package (`from bvh import RayTracer`, scene/gaussian_model.py:16) and
 `relightable3dgaussian_amd.simple_knn` as its `simple_knn` extension (`from simple_knn._C import
 distCUDA2`, scene/gaussian_model.py:13) (INTEGRATION.md).
+
+`relightable3dgaussian_amd.loss` is the training image loss (`ssim` of utils/loss_utils.py and the
+fused L1 + SSIM term of calculate_loss).
 """
 from __future__ import annotations
 

@@ -824,6 +824,84 @@ torch::Tensor dist_cuda2(const torch::Tensor& points) {
     return out;
 }
 
+// ---- image loss (utils/loss_utils.py:31-62 ssim, neilf.py:216-222) --------------------------------
+
+// img: [..., H, W] planes (hwc false) or the rasterizer's [H, W, C] (hwc true); gt always [..., H, W]
+// with as many planes. The checked, contiguous pair and the geometry the C ABI wants.
+struct LossImages {
+    torch::Tensor img, gt;
+    int64_t planes, H, W, img_stride[3];
+};
+LossImages loss_images(const torch::Tensor& img, const torch::Tensor& gt, bool hwc, const char* what) {
+    TORCH_CHECK(img.scalar_type() == torch::kFloat32 && gt.scalar_type() == torch::kFloat32, what,
+                ": expected float32");
+    TORCH_CHECK(gt.dim() >= 2, what, ": gt [..., H, W] expected");
+    LossImages r;
+    r.H = gt.size(-2);
+    r.W = gt.size(-1);
+    r.planes = r.H * r.W ? gt.numel() / (r.H * r.W) : 0;
+    if (hwc) {
+        TORCH_CHECK(img.dim() == 3 && gt.dim() == 3 && img.size(0) == r.H && img.size(1) == r.W &&
+                        img.size(2) == gt.size(0),
+                    what, ": shape mismatch: img [H,W,C] against gt [C,H,W] expected");
+        r.img_stride[0] = 1, r.img_stride[1] = r.W * r.planes, r.img_stride[2] = r.planes;
+    } else {
+        TORCH_CHECK(img.sizes() == gt.sizes(), what, ": shape mismatch between img and gt");
+        r.img_stride[0] = r.H * r.W, r.img_stride[1] = r.W, r.img_stride[2] = 1;
+    }
+    TORCH_CHECK(gt.numel() <= (int64_t)INT32_MAX, what, ": planes * H * W exceeds int32");
+    TORCH_CHECK(img.is_cuda() && gt.is_cuda(), what, ": expected GPU tensors (this build has no CPU path)");
+    TORCH_CHECK(img.device() == gt.device(), what, ": img and gt on different devices");
+    r.img = img.contiguous();
+    r.gt = gt.contiguous();
+    return r;
+}
+
+// -> (sums [planes, 3]: per plane the sums of ssim_map, |img - gt|, (img - gt)^2; dmaps [3, planes, H, W]
+// for image_loss_backward, or an empty tensor when need_grad is false)
+std::tuple<torch::Tensor, torch::Tensor> image_loss_forward(const torch::Tensor& img, const torch::Tensor& gt,
+                                                            bool hwc, bool need_grad) {
+    const auto a = loss_images(img, gt, hwc, "image_loss_forward");
+    const c10::OptionalDeviceGuard guard(a.img.device());
+    auto sums = a.gt.numel() ? torch::empty({a.planes, 3}, a.img.options()) : torch::zeros({a.planes, 3}, a.img.options());
+    auto dmaps = need_grad ? torch::empty({3, a.planes, a.H, a.W}, a.img.options()) : torch::empty({0}, a.img.options());
+    TensorAlloc scratch{a.img.options().dtype(torch::kUInt8), {}};
+    check(r3dg_image_loss_forward((int)a.planes, (int)a.H, (int)a.W, a.img.data_ptr<float>(), a.img_stride[0],
+                                  a.img_stride[1], a.img_stride[2], a.gt.data_ptr<float>(), a.H * a.W, a.W, 1,
+                                  sums.data_ptr<float>(), need_grad && dmaps.numel() ? dmaps.data_ptr<float>() : nullptr,
+                                  tensor_alloc, &scratch, stream_of(a.img.device())),
+          "image_loss_forward");
+    return {sums, dmaps};
+}
+
+// -> dL/dimg, shaped and laid out like img: scale * (w_ssim * d(sum ssim_map)/dimg + w_abs * sign(img - gt))
+// per plane, the weights read on the device (an absent scale is 1)
+torch::Tensor image_loss_backward(const torch::Tensor& img, const torch::Tensor& gt, bool hwc,
+                                  const torch::Tensor& dmaps, const torch::Tensor& w_ssim, const torch::Tensor& w_abs,
+                                  const std::optional<torch::Tensor>& scale) {
+    const auto a = loss_images(img, gt, hwc, "image_loss_backward");
+    auto weight = [&](const torch::Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.device() == a.img.device() && t.scalar_type() == torch::kFloat32 &&
+                        t.numel() == a.planes,
+                    "image_loss_backward: ", name, " float32 [planes] on the images' device expected");
+        return t.contiguous();
+    };
+    TORCH_CHECK(dmaps.is_cuda() && dmaps.device() == a.img.device() && dmaps.scalar_type() == torch::kFloat32 &&
+                    dmaps.numel() == 3 * a.gt.numel(),
+                "image_loss_backward: dmaps float32 [3,planes,H,W] from image_loss_forward(need_grad=True) expected");
+    const auto d = dmaps.contiguous(), ws = weight(w_ssim, "w_ssim"), wa = weight(w_abs, "w_abs");
+    const auto sc = scale ? weight(*scale, "scale") : torch::Tensor();
+    const c10::OptionalDeviceGuard guard(a.img.device());
+    auto out = torch::empty_like(a.img);
+    check(r3dg_image_loss_backward((int)a.planes, (int)a.H, (int)a.W, a.img.data_ptr<float>(), a.img_stride[0],
+                                   a.img_stride[1], a.img_stride[2], a.gt.data_ptr<float>(), a.H * a.W, a.W, 1,
+                                   d.data_ptr<float>(), ws.data_ptr<float>(), wa.data_ptr<float>(),
+                                   scale ? sc.data_ptr<float>() : nullptr, out.data_ptr<float>(),
+                                   stream_of(a.img.device())),
+          "image_loss_backward");
+    return out;
+}
+
 // trace_bvh_opacity (bvh/src/bvh.cu:87-117): outputs shaped like rays_o without its last axis
 std::tuple<torch::Tensor, torch::Tensor> trace_bvh_opacity(const torch::Tensor& nodes, const torch::Tensor& aabbs,
                                                            const torch::Tensor& rays_o, const torch::Tensor& rays_d,
@@ -979,6 +1057,15 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("bvh_leaf_aabbs", &bvh_leaf_aabbs);
     // nearest-neighbour distances: the reference's simple_knn._C (submodules/simple-knn/ext.cpp)
     m.def("distCUDA2", &dist_cuda2);
+    // the fused L1 + SSIM image loss (relightable3dgaussian_amd/loss.py)
+    m.def("image_loss_forward", &image_loss_forward, py::arg("img"), py::arg("gt"), py::arg("hwc"),
+          py::arg("need_grad"));
+    m.def("image_loss_backward", &image_loss_backward, py::arg("img"), py::arg("gt"), py::arg("hwc"),
+          py::arg("dmaps"), py::arg("w_ssim"), py::arg("w_abs"), py::arg("scale") = py::none());
+    m.def("image_loss_window", []() {
+        const float* w = r3dg_image_loss_window();
+        return std::vector<float>(w, w + 11);
+    });
     m.def("profile_enable", [](int64_t n) { check(r3dg_profile_enable((int)n), "profile_enable"); });
     m.def("profile_read", [](int64_t kernel) {
         int c = 0;
