@@ -277,16 +277,14 @@ __global__ void __launch_bounds__(256) brdf_fwd_kernel(BrdfKArgs a) {
 // alternatives, all slower at P = 1M: the coefficients staged in LDS at 2 waves/SIMD (spills;
 // 3.9 ms incl. the old reducer), 2 waves/SIMD with registers only (spills, 3.3 ms), the sample
 // loop unrolled by 2 / 3 (accumulators move to AGPRs), the environment SH re-read through the
-// scalar cache each sample (R3DG_BRDF_ENV_RELOAD: no SGPR spills but exposed latency, +0.27 ms).
+// scalar cache each sample (no SGPR spills but exposed latency, +0.27 ms).
 // What paid: the next sample's direction loaded one iteration ahead, per-Gaussian BRDF terms
 // hoisted (eval_brdf_fast), reciprocal multiplications instead of divisions, products instead of
 // powf, compile-time loop bounds in the S = 16 specialisation (1051 -> 514 VALU per sample), and
 // a parallel env-gradient reducer (brdf_dir_reduce_kernel): 2.33 -> 0.58 ms in all.
-#ifndef R3DG_BRDF_REG_WAVES
-#define R3DG_BRDF_REG_WAVES 1
-#endif
+constexpr int kBrdfRegWaves = 1;
 template <int NI, int ND, int NV>
-__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(R3DG_BRDF_REG_WAVES)))
+__global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(kBrdfRegWaves)))
 brdf_bwd_kernel(BrdfKArgs a) {
     constexpr int NDA = 16;  // register accumulators for dL_ddirect_shs (S_direct <= 16)
     const r3dg_brdf_inputs& in = a.in;
@@ -340,13 +338,10 @@ brdf_bwd_kernel(BrdfKArgs a) {
             float coef[16];
             sh_coef16(d.x, d.y, d.z, coef);
             Sample s;
-            // R3DG_BRDF_ENV_RELOAD: the environment SH pointer laundered per sample, so its 48
-            // values are re-read through the scalar cache instead of held in SGPRs (no SGPR spills,
-            // but the reloads' latency shows at one wave per SIMD: measured slower)
+            // (the environment SH pointer laundered per sample, so that its 48 values are re-read
+            // through the scalar cache instead of held in SGPRs: no SGPR spills, but the reloads'
+            // latency shows at one wave per SIMD, measured slower)
             const float* env = in.direct_shs;
-#ifdef R3DG_BRDF_ENV_RELOAD
-            asm volatile("" : "+s"(env));
-#endif
             if constexpr (NI > 0)
                 eval_lights<NI, ND, NV>(coef, inc_r, NI, env, ND, vis_r, NV, s);
             else

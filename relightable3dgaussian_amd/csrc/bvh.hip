@@ -418,10 +418,9 @@ __global__ void __launch_bounds__(256) bvh_ray_morton_kernel(int R, const float*
     index[i] = (uint32_t)i;
 }
 
-#ifndef R3DG_BVH_LDS
-#define R3DG_BVH_LDS 16  // measured: 8 / 12 / 16 / 24 / 32 entries (tools/exp_bvh.sh); 16 fills 7 waves per SIMD
-#endif
-constexpr int kLdsStack = R3DG_BVH_LDS;  // per-lane stack entries in LDS ([entry][lane]: conflict-free)
+// per-lane stack entries in LDS ([entry][lane]: conflict-free); measured: 8 / 12 / 16 / 24 / 32 entries,
+// 16 fills 7 waves per SIMD
+constexpr int kLdsStack = 16;
 // Group cut in the log domain. Every term a lane adds is __logf(1 - alpha) + kLogSlack, where
 // kLogSlack bounds, per term, everything that separates the running sum from log of the
 // reference's single-chain product: v_log_f32 (<= 1 ulp of a log2 in [-0.152, 0]: 1.5e-8), the ln 2

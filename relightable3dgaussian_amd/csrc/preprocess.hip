@@ -11,9 +11,7 @@
 #include "r3dg_kernels.h"
 #include "r3dg_tilesort.h"
 
-#ifndef R3DG_SORT_LONG_IPT
-#define R3DG_SORT_LONG_IPT 8  // items per thread of the depth sort for tiles longer than 1024 instances
-#endif
+constexpr int kSortLongIPT = 8;  // items per thread of the depth sort for tiles longer than 1024 instances
 
 namespace r3dg {
 
@@ -362,7 +360,7 @@ __global__ void __launch_bounds__(1024) bin_colscan_kernel(BinArgs a, uint2* __r
     // the wave's rows of the column held in registers: all loads in flight at once, and the offsets
     // pass below writes from them (a loop of dependent loads, twice: 20.2 -> 15.5 us at M1,
     // profiles/r06/colscan_regs/)
-    constexpr int kRows = (R3DG_BIN_BLOCKS_MAX + 15) / 16;  // r1 - r0 <= ceil(nblk / 16)
+    constexpr int kRows = (kBinBlocksMax + 15) / 16;  // r1 - r0 <= ceil(nblk / 16)
     uint32_t c[kRows];
     uint32_t s = 0;
 #pragma unroll
@@ -712,7 +710,7 @@ hipError_t launch_bin_order(const BinArgs& a, uint2* ranges, uint32_t* order, hi
 // buffers, ping-pong, landing in point_list.
 union TileDepthSortStorage {
     TileSortLds<4> s4;
-    TileSortLds<R3DG_SORT_LONG_IPT> sl;
+    TileSortLds<kSortLongIPT> sl;
 };
 
 __device__ __forceinline__ uint32_t nt_load(const uint32_t* p) { return __builtin_nontemporal_load(p); }
@@ -751,10 +749,8 @@ __device__ __forceinline__ void sort_tile_chunks(uint32_t s, uint32_t n, uint32_
     }
 }
 
-#ifndef R3DG_SORT_WAVES
-#define R3DG_SORT_WAVES 6  // waves per SIMD the long-tile sorter's registers target (80 VGPR; 8: 64, spills)
-#endif
-__global__ void __launch_bounds__(kSortBT) __attribute__((amdgpu_waves_per_eu(R3DG_SORT_WAVES)))
+constexpr int kSortWaves = 6;  // waves per SIMD the long-tile sorter's registers target (80 VGPR; 8: 64, spills)
+__global__ void __launch_bounds__(kSortBT) __attribute__((amdgpu_waves_per_eu(kSortWaves)))
 tile_depth_sort_kernel(int T, const uint2* __restrict__ ranges, const uint32_t* __restrict__ order,
                        const uint2* __restrict__ pairs, uint32_t* __restrict__ point_list,
                        uint32_t* kA, uint32_t* vA, uint32_t* kB, int min_n) {
@@ -772,7 +768,7 @@ tile_depth_sort_kernel(int T, const uint2* __restrict__ ranges, const uint32_t* 
     }
     // sorter capacity by tile length (block-uniform); a 2-item sorter for tiles of up to 512
     // instances measured no faster (M1: 0.086 vs 0.083 ms, it spills one VGPR)
-    const uint32_t kChunk = n <= kSortBT * 4 ? kSortBT * 4 : kSortBT * R3DG_SORT_LONG_IPT;
+    const uint32_t kChunk = n <= kSortBT * 4 ? kSortBT * 4 : kSortBT * kSortLongIPT;
     const uint32_t nchunks = (n + kChunk - 1) / kChunk;
     int rounds = 0;
     while ((1u << rounds) < nchunks) ++rounds;
@@ -782,7 +778,7 @@ tile_depth_sort_kernel(int T, const uint2* __restrict__ ranges, const uint32_t* 
     if (kChunk == kSortBT * 4)
         sort_tile_chunks<4>(s, n, nchunks, pairs, rk, rv, storage.s4);
     else
-        sort_tile_chunks<R3DG_SORT_LONG_IPT>(s, n, nchunks, pairs, rk, rv, storage.sl);
+        sort_tile_chunks<kSortLongIPT>(s, n, nchunks, pairs, rk, rv, storage.sl);
     if (nchunks == 1) return;
     __syncthreads();
     uint32_t *sk = rk, *sv = rv, *dk = (rk == kA) ? kB : kA, *dv = (rk == kA) ? point_list : vA;

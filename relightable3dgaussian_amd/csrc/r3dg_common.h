@@ -346,38 +346,19 @@ __device__ __forceinline__ float fast_expf(float x) {
 // away from a 4e-6 band the decision equals the exact one; inside the band the step re-evaluates
 // with r3dg_expf (rare; one wave-uniform branch). Returns the exact-decision G.
 __device__ __forceinline__ float settle_threshold(float power, float opacity, float G) {
-#ifdef R3DG_HWEXP
-    return G;
-#endif
     const bool near = fabsf(__builtin_fmaf(opacity * G, 255.0f, -1.0f)) < 4e-6f;
-#ifndef R3DG_NOSETTLE
     if (__builtin_expect(__ballot(near) != 0ull, 0)) {
         if (near) G = r3dg_expf(power);
     }
-#else
-    (void)near;
-#endif
     return G;
 }
 
-// The blend's G = exp(power) in the forward kernels. Default: the shared bit-reproducible
-// r3dg_expf (n_contrib / final_T bit-exact against the oracle). R3DG_HWEXP (experiment build,
-// DESIGN.md §4): the hardware v_exp_f32 on power * log2(e) -- the backward's fast_expf, so forward
-// and backward take identical alpha decisions without the backward's settle step, but the bits are
-// not the oracle's (v_exp_f32 is not correctly rounded: tools/probe/vexp_cr.hip).
-__device__ __forceinline__ float blend_expf(float x) {
-#ifdef R3DG_HWEXP
-    return fast_expf(x);
-#else
-    return r3dg_expf(x);
-#endif
-}
+// The forward kernels' G = exp(power) is the shared bit-reproducible r3dg_expf (n_contrib / final_T
+// bit-exact against the oracle). The hardware v_exp_f32 in both directions, without the settle step,
+// was measured and removed: its bits are not the oracle's (tools/probe/vexp_cr.hip).
 
 // settle_threshold for a pair of steps with one wave-uniform branch.
 __device__ __forceinline__ void settle_threshold2(float pw0, float o0, float& G0, float pw1, float o1, float& G1) {
-#ifdef R3DG_HWEXP
-    return;  // the forward used the same fast_expf: its decisions are these
-#endif
     const bool n0 = fabsf(__builtin_fmaf(o0 * G0, 255.0f, -1.0f)) < 4e-6f;
     const bool n1 = fabsf(__builtin_fmaf(o1 * G1, 255.0f, -1.0f)) < 4e-6f;
     if (__builtin_expect(__ballot(n0 || n1) != 0ull, 0)) {
@@ -415,20 +396,12 @@ __device__ __forceinline__ float qform_min_rect(float a, float b, float c, float
 // needle-shaped splats far from their mean the terms reach ~1e6 and cancel to a few units, and the
 // term keeps the cull conservative there (tests/test_gpu_parity.py test_cull_exact_needles:
 // cull on == off bit for bit on 1920x1080 needles with sigma up to 1000 px). Round 1 used m = 0.1.
-#ifndef R3DG_CULL_MARGIN
-#define R3DG_CULL_MARGIN 0.01f
-#endif
-#ifndef R3DG_CULL_REL
-#define R3DG_CULL_REL 1e-6f  // e: 16 * 2^-24 rounded up
-#endif
+constexpr float kCullMargin = 0.01f;  // m
+constexpr float kCullRel = 1e-6f;     // e: 16 * 2^-24 rounded up
 // Forward blend: read a staged attribute row's last float4 whole even when its last channel is
 // padding (S = 11: 15 channels), so it is one ds_read_b128 rather than a ds_read_b96 (twice the
 // LDS-array cycles, MI355X_MICROARCH.md §LDS): render_fwd 0.515 -> 0.507 ms at M1 (three same-box
 // pairs, profiles/r06/b128_prio_ab; the backward measured +0.4 % with it and keeps the b96).
-// 0 restores the narrow read (experiment builds).
-#ifndef R3DG_ATTR_B128
-#define R3DG_ATTR_B128 1
-#endif
 
 // Is min Q over the pixel rectangle [xa, xb] x [ya, yb] above t (1 + m) + m + e * Mmax, i.e. does
 // alpha = o exp(-Q/2) stay below 1/255 at every pixel of the rectangle, in the blend's own fp32
@@ -440,8 +413,8 @@ __device__ __forceinline__ bool rect_culled(float4 co, float mx, float my, float
     const float dxa = mx - xa, dxb = mx - xb, dya = my - ya, dyb = my - yb;
     const float ab = fabsf(co.y);
     const float mmax = (co.x + ab) * fmaxf(dxa * dxa, dxb * dxb) + (co.z + ab) * fmaxf(dya * dya, dyb * dyb);
-    const float t = 2.0f * __logf(255.0f * co.w) * (1.0f + R3DG_CULL_MARGIN) + R3DG_CULL_MARGIN +
-                    R3DG_CULL_REL * mmax;
+    const float t = 2.0f * __logf(255.0f * co.w) * (1.0f + kCullMargin) + kCullMargin +
+                    kCullRel * mmax;
     return qmin > t;  // false for a NaN / infinite bound: keep
 }
 
@@ -456,36 +429,6 @@ __device__ __forceinline__ bool quadrant_live(float2 xy, float4 staged, float qx
     const float det = co.x * co.z - co.y * co.y;
     if (!(det > 0.0f) || !(co.x > 0.0f) || !(co.z > 0.0f)) return true;
     return !rect_culled(co, xy.x, xy.y, qx, qx + 7.0f, qy, qy + 7.0f);
-}
-
-// quadrant_live for the quadrant's two 8x4 halves (rows qy..qy+3, qy+4..qy+7): the threshold, the
-// conic's reciprocals and Mmax over the whole quadrant (an upper bound of each half's: still
-// conservative) are shared; the form's minimum is taken over each half's rectangle.
-// The rectangle's edges come in wave-uniform (SGPR: readfirstlane by the caller), so they cost
-// no VGPRs in the 64-VGPR forward.
-__device__ __forceinline__ float uniform_f(float x) {
-    return __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(x)));
-}
-__device__ __forceinline__ void half_live(float2 xy, float4 staged, float xa, float xb, float ya, float ym0,
-                                          float ym1, float yb, int cull, bool& top, bool& bot) {
-    top = bot = true;
-    if (!cull) return;
-    const float4 co = unstage_conic(staged);
-    if (co.w < 1.0f / 255.0f) {
-        top = bot = false;
-        return;
-    }
-    const float det = co.x * co.z - co.y * co.y;
-    if (!(det > 0.0f) || !(co.x > 0.0f) || !(co.z > 0.0f)) return;
-    const float mx = xy.x, my = xy.y;
-    const float ia = __builtin_amdgcn_rcpf(co.x), ic = __builtin_amdgcn_rcpf(co.z);
-    const float dxa = mx - xa, dxb = mx - xb, dya = my - ya, dyb = my - yb;
-    const float ab = fabsf(co.y);
-    const float mmax = (co.x + ab) * fmaxf(dxa * dxa, dxb * dxb) + (co.z + ab) * fmaxf(dya * dya, dyb * dyb);
-    const float t = 2.0f * __logf(255.0f * co.w) * (1.0f + R3DG_CULL_MARGIN) + R3DG_CULL_MARGIN +
-                    R3DG_CULL_REL * mmax;
-    top = !(qform_min_rect(co.x, co.y, co.z, ia, ic, mx, my, xa, xb, ya, ym0) > t);
-    bot = !(qform_min_rect(co.x, co.y, co.z, ia, ic, mx, my, xa, xb, ym1, yb) > t);
 }
 
 }  // namespace r3dg

@@ -69,15 +69,11 @@ constexpr int kBinBucketShift = 28;  // the tile's index in its bucket above the
 constexpr int kBinThreads = 1024;                  // binning workgroup (one per CU)
 constexpr int kBinSub = 1024;                      // Gaussians staged in LDS at a time
 constexpr int kBinMaxTiles = (163840 - 16 * kBinSub) / 4;  // LDS counters per workgroup (160 KiB)
-// binning workgroups for T tiles: the [nblk, T] count matrix stays <= 4 * R3DG_BIN_MATRIX entries
-#ifndef R3DG_BIN_BLOCKS_MAX
-#define R3DG_BIN_BLOCKS_MAX 256
-#endif
-#ifndef R3DG_BIN_MATRIX
-#define R3DG_BIN_MATRIX (1 << 21)
-#endif
+// binning workgroups for T tiles: the [nblk, T] count matrix stays <= kBinMatrix entries
+constexpr int kBinBlocksMax = 256;
+constexpr int kBinMatrix = 1 << 21;
 inline int bin_blocks_max(int T) {
-    return T > kBinMaxTiles ? 0 : std::max(1, std::min(R3DG_BIN_BLOCKS_MAX, R3DG_BIN_MATRIX / std::max(T, 1)));
+    return T > kBinMaxTiles ? 0 : std::max(1, std::min(kBinBlocksMax, kBinMatrix / std::max(T, 1)));
 }
 
 struct RenderFwdArgs {
@@ -280,9 +276,7 @@ __device__ __forceinline__ uint32_t instance_slot(const uint32_t* offsets, float
     get_rect(xy.x, xy.y, radius, grid_x, grid_y, x0, y0, x1, y1);
     return (g == 0 ? 0u : offsets[g - 1]) + (uint32_t)((ty - y0) * (x1 - x0) + (tx - x0));
 }
-#ifndef R3DG_XYZ_R
-#define R3DG_XYZ_R 4  // tile rows per xyz_normal_kernel workgroup (render_fwd.hip; 1 / 2 / 4 / 8: 25.7 / 25.0 / 21.7 / 24.9 us at M1)
-#endif
+constexpr int kXyzRows = 4;  // tile rows per xyz_normal_kernel workgroup (render_fwd.hip; 1 / 2 / 4 / 8: 25.7 / 25.0 / 21.7 / 24.9 us at M1)
 __global__ void xyz_normal_kernel(XyzNormalArgs a);
 constexpr int kOrderSlices = 16;  // xyz_normal_kernel's leading workgroups that sort the backward's tile order
 // RenderIntermediateTextures: packs the per-Gaussian depth / stencil record, then the DMA-staged blend
@@ -312,14 +306,12 @@ __host__ __device__ inline int smax_of(int S) {
 }
 __host__ __device__ inline int record_f4(int S) { return 2 + (4 + smax_of(S) + 3) / 4; }
 __host__ __device__ inline int bwd_xblocks(int S) { return (4 + smax_of(S) + 15) / 16; }
-// partial-row stride (floats): X part + 6 moments + 2 pad, rounded up to R3DG_ROW_ALIGN floats.
-// Rows of whole 128-byte lines (R3DG_ROW_ALIGN 32) measured slower: row-sum 0.235 -> 0.246 ms,
+// partial-row stride (floats): X part + 6 moments + 2 pad, rounded up to kRowAlign floats.
+// Rows of whole 128-byte lines (kRowAlign 32) measured slower: row-sum 0.235 -> 0.246 ms,
 // gather 0.144 -> 0.152 ms at M1 (more bytes per present row, no fewer lines touched).
-#ifndef R3DG_ROW_ALIGN
-#define R3DG_ROW_ALIGN 8
-#endif
+constexpr int kRowAlign = 8;
 __host__ __device__ inline int part_row_stride(int S) {
-    return (16 * bwd_xblocks(S) + 8 + R3DG_ROW_ALIGN - 1) / R3DG_ROW_ALIGN * R3DG_ROW_ALIGN;
+    return (16 * bwd_xblocks(S) + 8 + kRowAlign - 1) / kRowAlign * kRowAlign;
 }
 
 __host__ __device__ inline int padded_tile_grid(int num_tiles) { return (num_tiles + 7) & ~7; }
@@ -336,8 +328,8 @@ __device__ __forceinline__ int block_tile(const uint32_t* order, int num_tiles) 
     if (order) return (int)order[b];
     return xcd_tile(b, gridDim.x);
 }
-#ifdef R3DG_EXP_COUNT  // timing/counting experiment builds only (tools/exp_build.sh)
-static __device__ unsigned long long g_exp_cnt[8];  // one copy per translation unit
+#ifdef R3DG_EXP_COUNT  // the counting build only (tools/exp_build.sh; its results are valid)
+static __device__ unsigned long long g_exp_cnt[4];  // one copy per translation unit
 #define R3DG_EXP_READER(name)                                                        \
     extern "C" void name(unsigned long long* out) {                                  \
         hipMemcpyFromSymbol(out, HIP_SYMBOL(g_exp_cnt), sizeof(g_exp_cnt));         \

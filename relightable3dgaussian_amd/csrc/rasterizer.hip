@@ -921,7 +921,7 @@ static int stage_blend(ForwardCtx& c) {
         xa.bwd_order = T > 0 ? img.bwd_order : nullptr;
         xa.blocks_x = p.gx;
         hipLaunchKernelGGL(xyz_normal_kernel,
-                           dim3((T > 0 ? kOrderSlices : 0) + p.gx * ((p.gy + R3DG_XYZ_R - 1) / R3DG_XYZ_R)), dim3(256),
+                           dim3((T > 0 ? kOrderSlices : 0) + p.gx * ((p.gy + kXyzRows - 1) / kXyzRows)), dim3(256),
                            0, st, xa);
         R3DG_CHECK_LAUNCH(s->debug, st);
     } else {

@@ -242,15 +242,15 @@ __device__ __forceinline__ void wave_lds_sync() {
     __builtin_amdgcn_wave_barrier();
 }
 
-// Tuning knobs (experiment builds override them through R3DG_EXTRA_HIPFLAGS). Occupancy is set
-// by LDS and VGPRs together; the LDS allocation is rounded up in 2 KiB steps.
+// Tuning constants: each is declared once, next to its measurement, and has no -D override. A
+// tuning A/B edits the constant on a branch and builds that tree into a library directory of its
+// own (build.py R3DG_LIB_DIR / R3DG_OBJ_DIR; tools/ab_libs.sh). Occupancy is set by LDS and VGPRs
+// together; the LDS allocation is rounded up in 2 KiB steps.
 typedef float f32x2 __attribute__((ext_vector_type(2)));
-#ifndef R3DG_BWD_WAVES
-#define R3DG_BWD_WAVES 3  // waves per SIMD the register allocation targets (SMAX <= 12). The kernel
-                          // takes 125 VGPRs either way and runs 4 waves per SIMD (LDS: 4 blocks per
-                          // CU); the target of 3 only changes the scheduler's latency / pressure
-                          // trade-off: render_bwd -0.4 % at M1 (4 pairs), -0.8 % at C3, round 5
-#endif
+constexpr int kBwdWaves = 3;  // waves per SIMD the register allocation targets (SMAX <= 12). The kernel
+                              // takes 125 VGPRs either way and runs 4 waves per SIMD (LDS: 4 blocks per
+                              // CU); the target of 3 only changes the scheduler's latency / pressure
+                              // trade-off: render_bwd -0.4 % at M1 (4 pairs), -0.8 % at C3, round 5
 
 // w|q image: row r (0..15 w, 16..31 q) of 64 pixels, padded stride WQS = 66 floats; pixel c of
 // row r at r*WQS + c. ds_read_b32 / ds_write_b32 bank by dword address mod 32 within each 32-lane
@@ -296,17 +296,12 @@ __device__ __forceinline__ void split_bf16x3(const float (&x)[8], bf16x8& h, bf1
     o = O.v;
 }
 
-#ifndef R3DG_BWD_SPLIT
-#define R3DG_BWD_SPLIT 2  // bf16 terms per f32 value of w (= alpha T: colour / feature / depth grads)
-                          // in the flush's MFMA products: 2 = h + m, |x - h - m| <= 2^-16 |x|
-                          // unbiased; 3 = exact f32 products
-#endif
-#ifndef R3DG_BWD_SPLIT_Q
-#define R3DG_BWD_SPLIT_Q 3  // the same for q = G dL/dalpha (the moments behind the mean2D / conic /
-                            // opacity grads): exact, as the conic inverse amplifies their errors by up
-                            // to ~1e6 on needle-shaped splats (test_cull_exact_needles: with 2 terms
-                            // one needle's dL/dmeans3D left the fp32 sensitivity bound 88x)
-#endif
+constexpr int kBwdSplit = 2;  // bf16 terms per f32 value of w (= alpha T: colour / feature / depth grads)
+                              // in the flush's MFMA products: 2 = h + m, |x - h - m| <= 2^-16 |x|
+                              // unbiased; 3 = exact f32 products
+// q = G dL/dalpha (the moments behind the mean2D / conic / opacity grads) always takes three terms:
+// exact, as the conic inverse amplifies their errors by up to ~1e6 on needle-shaped splats
+// (test_cull_exact_needles: with 2 terms one needle's dL/dmeans3D left the fp32 sensitivity bound 88x)
 
 // x = h + m to within 2^-16 |x|: h the truncated top 8 significant bits (v_and + v_perm per pair),
 // m = x - h (exact) rounded to nearest bf16 (one v_cvt_pk_bf16_f32 per pair), so the residual is
@@ -331,29 +326,12 @@ __device__ __forceinline__ void split_bf16x2(const float (&x)[8], bf16x8& h, bf1
     m = M.v;
 }
 
-// the atomic flush's add (timing-only builds swap it: tools/exp_build.sh)
-#ifdef R3DG_EXP_ATOMSTORE  // timing experiment only (results invalid): plain stores for the atomics
-#define R3DG_FLUSH_ADD(p, v) (*(p) = (v))
-#elif defined(R3DG_EXP_NOSTORE)  // timing experiment only (results invalid): the epilogue without its stores
-#define R3DG_FLUSH_ADD(p, v) do { if ((v) == 1.2345e-30f) *(p) = 0.f; } while (0)
-#else
-#define R3DG_FLUSH_ADD(p, v) atomicAdd((p), (v))
-#endif
-#ifndef R3DG_BWD_SWALK
-#define R3DG_BWD_SWALK 1  // the pair loop's live-mask walk by s_ff1 + s_bitset0 (inline asm), as the forward's
-#endif
-#ifndef R3DG_BWD_ORIGIN_MOMENTS
-#define R3DG_BWD_ORIGIN_MOMENTS 1  // atomic flush: moments re-centred on the image origin in the D lanes
-                                   // (gather_bwd_kernel expands them about the mean); 0: expanded about
-                                   // the mean in the flush through LDS tiles (round 5)
-#endif
-#ifndef R3DG_BWDG_NB
-#define R3DG_BWDG_NB 64  // instances per staged batch of the DMA-staged kernel
-#endif
-#ifndef R3DG_BWDG_GRP
-#define R3DG_BWDG_GRP 13  // instances per MFMA group of the DMA-staged kernel (64 / 13 measured best of
-                          // 32 / 16, 64 / 12, 64 / 13, 32 / 12: the smaller w|q image buys the larger batch)
-#endif
+// Measured and removed: the live-mask walk in plain C++ instead of s_ff1 + s_bitset0, and
+// the atomic flush's moments expanded about the mean in the flush through LDS tiles (round 5) instead
+// of re-centred on the image origin in the D lanes (gather_bwd_kernel expands them about the mean).
+constexpr int kBwdNB = 64;   // instances per staged batch of the DMA-staged kernel
+constexpr int kBwdGrp = 13;  // instances per MFMA group of the DMA-staged kernel (64 / 13 measured best of
+                             // 32 / 16, 64 / 12, 64 / 13, 32 / 12: the smaller w|q image buys the larger batch)
 
 // ---------------------------------------------------------------------------------------------
 // The backward blend (default). One 256-thread workgroup per tile (longest tiles first), wave w =
@@ -371,18 +349,18 @@ __device__ __forceinline__ void split_bf16x2(const float (&x)[8], bf16x8& h, bf1
 // [P, SRS] (the reference's own accumulation, backward.cu:552-611, at one atomic per channel per
 // (instance, wave) instead of per pixel): no partial rows, no row flags, no row_sum_kernel; sums
 // depend on the atomics' arrival order. !ATOM: the deterministic partial rows + row_sum_kernel.
-// WS: bf16 terms of w in the X products (R3DG_BWD_SPLIT, default 2); WS = 1 is the one-term
+// WS: bf16 terms of w in the X products (kBwdSplit, default 2); WS = 1 is the one-term
 // reduction the gradient parity bar must reject (R3DG_BWD_WTERMS=1, tests/test_gpu_parity.py
 // test_one_term_reduction_fails_bar).
-template <int SMAX, bool ATOM, int WS = R3DG_BWD_SPLIT>
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SMAX <= 12 ? R3DG_BWD_WAVES : 1)))
+template <int SMAX, bool ATOM, int WS = kBwdSplit>
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SMAX <= 12 ? kBwdWaves : 1)))
 render_bwd_glds_kernel(RenderBwdArgs a) {
-    constexpr int NB = R3DG_BWDG_NB;              // instances per batch (two batches staged)
+    constexpr int NB = kBwdNB;                    // instances per batch (two batches staged)
     constexpr int NW = 4;                         // waves per workgroup
     constexpr int NA4 = (4 + SMAX + 3) / 4;
     constexpr int NXB = (4 + SMAX + 15) / 16;
     constexpr int XW = 16 * NXB;
-    constexpr int GRP = R3DG_BWDG_GRP;            // instances per MFMA group (<= 16 A rows)
+    constexpr int GRP = kBwdGrp;                  // instances per MFMA group (<= 16 A rows)
     constexpr int RF4 = 2 + NA4;                  // float4s per render record
     constexpr int NCP = (RF4 * NB + 63) / 64;     // DMA wave-instructions per batch
     constexpr int SBUF = RF4 * NB;                // float4s per staging buffer
@@ -470,8 +448,8 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
             const float4 rr = st[(2 + q) * NB + ju];
             v[4 * q] = rr.x; v[4 * q + 1] = rr.y; v[4 * q + 2] = rr.z; v[4 * q + 3] = rr.w;
         }
-        // (the last row stays a ds_read_b96 at S = 11: the forward's whole-float4 read, R3DG_ATTR_B128,
-        // measured +0.4 % here, profiles/r06/b128_prio_ab)
+        // (the last row stays a ds_read_b96 at S = 11: the forward's whole-float4 read measured
+        // +0.4 % here, profiles/r06/b128_prio_ab)
         const float alpha = fminf(0.99f, opacity * G);
         const bool ok = live && p < last && !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
         okv = ok;
@@ -526,16 +504,12 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
     const uint32_t srs = (uint32_t)a.SRS;
     auto flush = [&](int r) {
         if (l == 0) R3DG_EXP_ADD(1, 1);
-#ifdef R3DG_EXP_NOFLUSH  // timing experiment only (results invalid): no reduction, no rows
-        (void)r;
-        return;
-#endif
         wave_lds_sync();
         floatx4 accX[NXB], accY = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
         for (int xb = 0; xb < NXB; ++xb) accX[xb] = floatx4{0.f, 0.f, 0.f, 0.f};
         // w rows times the upstream gradients on the bf16 MFMA: X = X1 + X2 (two terms), w = h + m
-        // (R3DG_BWD_SPLIT = 2, default: m rounded to nearest, three products m X1, h X2, h X1) or
+        // (WS = 2, default: m rounded to nearest, three products m X1, h X2, h X1) or
         // w = h + m + o exactly (3: the five products above 2^-24, smallest first)
 #pragma unroll
         for (int b = 0; b < 2; ++b) {
@@ -579,37 +553,19 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
 #pragma unroll
             for (int i = 0; i < 8; ++i) qv[i] = src[i];
             bf16x8 h, m, o;
-#if R3DG_BWD_SPLIT_Q == 1  // timing experiment only (results inexact)
-            split_bf16x2(qv, h, m);
-            (void)o;
-            (void)m;
-            accY = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h, yb[b], accY, 0, 0, 0);
-#elif R3DG_BWD_SPLIT_Q == 2
-            split_bf16x2(qv, h, m);
-            (void)o;
-            accY = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h, yb[b], accY, 0, 0, 0);
-            accY = __builtin_amdgcn_mfma_f32_16x16x32_bf16(m, yb[b], accY, 0, 0, 0);
-#else
             split_bf16x3(qv, h, m, o);
             accY = __builtin_amdgcn_mfma_f32_16x16x32_bf16(h, yb[b], accY, 0, 0, 0);
             accY = __builtin_amdgcn_mfma_f32_16x16x32_bf16(m, yb[b], accY, 0, 0, 0);
             accY = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o, yb[b], accY, 0, 0, 0);
-#endif
         }
-        // Group row r's bookkeeping sits in the pad columns of its w|q image rows (written by lane 0
-        // at the visit): the instance's mean (x, y) at w row r, columns 64-65, and its Gaussian
-        // (ATOM) or partial row (4 * slot + quadrant) at q row r, column 64. Lane group g handles
-        // D rows 4g + i of accumulator element i: one broadcast LDS read per row and value.
+        // Group row r's bookkeeping sits in the pad column of its w|q image (written by lane 0 at the
+        // visit): its Gaussian (ATOM) or partial row (4 * slot + quadrant) at q row r, column 64. Lane
+        // group g handles D rows 4g + i of accumulator element i: one broadcast LDS read per row.
         uint32_t rid[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
             rid[i] = reinterpret_cast<const uint32_t*>(wq)[(GRP + (l >> 4) * 4 + i) * WQS + 64];
-#ifdef R3DG_EXP_NOEPI  // timing experiment only (results invalid): no expansion, no stores
-        if (accX[0][0] == 1.2345e-30f && accY[0] == 1.2345e-30f) a.sums[l] = accX[0][1] + accY[1] + rid[0];
-        wave_lds_sync();
-        return;
-#endif
-        if constexpr (ATOM && R3DG_BWD_ORIGIN_MOMENTS) {
+        if constexpr (ATOM) {
             // The moments about the quadrant centre re-centred on the image origin in double, in the
             // D registers' own lanes: lane c < 6 of each 16-lane row holds moment c of its rows
             // 4g + i, and G_c = s_c + ka s0 + kb s1 + kc s2 (the wave's constants for column c,
@@ -635,63 +591,9 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
                 float* dst = lane_sums + (uint64_t)rid[i] * srs;
 #pragma unroll
                 for (int xb = 0; xb < NXB; ++xb)
-                    if (ok && xb * 16 + nch < 4 + S) R3DG_FLUSH_ADD(dst + xb * 16, accX[xb][i]);
+                    if (ok && xb * 16 + nch < 4 + S) atomicAdd(dst + xb * 16, accX[xb][i]);
                 double* mom = reinterpret_cast<double*>(a.sums + (uint64_t)rid[i] * srs + XW);
-                if (ok && nch < 6) R3DG_FLUSH_ADD(mom + nch, ev[i]);
-            }
-            wave_lds_sync();
-            return;
-        } else if constexpr (ATOM) {
-            // The moments about the quadrant centre, expanded about the Gaussian's mean once per row
-            // and summed in double: D rows go through a 16 x 8 float tile in w rows 0-1 (free once
-            // the MFMA operands were read); lane rr = l & 15 expands row rr in double (expand_moments'
-            // formula) into a 16 x 6 double tile in w rows 2-5, and every lane adds its (row, moment)
-            // element with an f64 atomic into the per-Gaussian moment sums. A needle's expanded terms
-            // (|mean - pixel| ~ 1e3 px) are ~1e3-1e6 times the sums they cancel to: summed in f32 in
-            // arrival order, one Gaussian's dL/dmean2D came out 2370x past its conditioning bound
-            // (test_cull_exact_needles; profiles/r05/README.md).
-            float* const yt = wq;
-            auto yoff = [](int row) { return (row >> 3) * WQS + (row & 7) * 8; };
-            auto doff = [](int row) { return (2 + (row >> 2)) * WQS + (row & 3) * 16; };  // 8-B aligned
-            if (nch < 6) {
-#pragma unroll
-                for (int i = 0; i < 4; ++i) yt[yoff((l >> 4) * 4 + i) + nch] = accY[i];
-            }
-            wave_lds_sync();
-            if (l < 16) {
-                const float2* yr = reinterpret_cast<const float2*>(yt + yoff(l));
-                const float2 m01 = yr[0], m23 = yr[1], m45 = yr[2];
-                const float2 mxy = *reinterpret_cast<const float2*>(wq + l * WQS + 64);
-                const double s0 = m01.x, s1 = m01.y, s2 = m23.x, s3 = m23.y, s4 = m45.x, s5 = m45.y;
-                const double dx0 = (double)mxy.x - (double)qcx, dy0 = (double)mxy.y - (double)qcy;
-                double* yw = reinterpret_cast<double*>(wq + doff(l));
-                yw[0] = s0;
-                yw[1] = dx0 * s0 - s1;
-                yw[2] = dy0 * s0 - s2;
-                yw[3] = dx0 * (dx0 * s0 - 2.0 * s1) + s3;
-                yw[4] = dx0 * (dy0 * s0 - s2) - dy0 * s1 + s4;
-                yw[5] = dy0 * (dy0 * s0 - 2.0 * s2) + s5;
-            }
-            wave_lds_sync();
-            // the four expanded elements of this lane, read together (the compiler would otherwise
-            // sink each read into its atomic's masked branch: four dependent LDS round trips)
-            double ev[4];
-#pragma unroll
-            for (int i = 0; i < 4; ++i)
-                ev[i] = reinterpret_cast<const double*>(wq + doff((l >> 4) * 4 + i))[nch < 6 ? nch : 0];
-            asm volatile("" ::"v"(ev[0]), "v"(ev[1]), "v"(ev[2]), "v"(ev[3]));
-#pragma unroll
-            for (int i = 0; i < 4; ++i) {
-                const int row = (l >> 4) * 4 + i;
-                // (only the atomics under lane masks; adding 0 from the masked lanes instead
-                // measured 23x slower: rows past the group all name one Gaussian and contend)
-                const bool ok = row < r;
-                float* dst = lane_sums + (uint64_t)rid[i] * srs;
-#pragma unroll
-                for (int xb = 0; xb < NXB; ++xb)
-                    if (ok && xb * 16 + nch < 4 + S) R3DG_FLUSH_ADD(dst + xb * 16, accX[xb][i]);
-                double* mom = reinterpret_cast<double*>(a.sums + (uint64_t)rid[i] * srs + XW);
-                if (ok && nch < 6) R3DG_FLUSH_ADD(mom + nch, ev[i]);
+                if (ok && nch < 6) atomicAdd(mom + nch, ev[i]);
             }
             wave_lds_sync();
             return;
@@ -752,16 +654,9 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
     int buf = 0;
-#ifdef R3DG_EXP_COUNT
-    const long long t_begin = wall_clock64();
-    long long t_wait = 0, t_mask = 0, t_flush = 0;
-#endif
     for (int hi = max_last; hi > 0; hi -= NB) {
         const int cnt = min(NB, hi);
         const int hn = hi - NB;
-#ifdef R3DG_EXP_COUNT
-        const long long tm0 = wall_clock64();
-#endif
         const uint32_t cbits = cb_next;
         const uint32_t gid_staged = gid_next;
         if (hn > 0) {  // block-uniform: stage the next batch while this one blends
@@ -788,16 +683,12 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
             row_l = 4 * slot + w;
             a.flags[row_l] = 1;
         }
-#ifdef R3DG_EXP_COUNT
         if (l == 0) R3DG_EXP_ADD(0, __builtin_popcountll(bits));
-        t_mask += wall_clock64() - tm0;
-#endif
         auto rec0 = [&](int j) { return st[__builtin_amdgcn_readfirstlane(j)]; };
         auto pos = [&](int j) {
             return *reinterpret_cast<const float2*>(st + NB + __builtin_amdgcn_readfirstlane(j));
         };
         while (bits) {
-#if R3DG_BWD_SWALK
             int j0, j1;
             if constexpr (NB > 32) {
                 unsigned long long b = bits;
@@ -812,13 +703,6 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
             }
             const bool has1 = j1 >= 0;
             j1 = has1 ? j1 : j0;
-#else
-            const int j0 = (int)__builtin_ctzll(bits);
-            bits &= bits - 1;
-            const bool has1 = bits != 0u;
-            const int j1 = has1 ? (int)__builtin_ctzll(bits) : j0;
-            bits &= bits - 1;
-#endif
             const float4 co0 = rec0(j0), co1 = rec0(j1);
             const float2 xy0 = pos(j0), xy1 = pos(j1);
             const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
@@ -829,18 +713,8 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
             bool ok0, ok1;
             step(j0, hi - 1 - j0, true, co0.w, pw0, G0, wv0, qv0, ok0);
             step(j1, hi - 1 - j1, has1, co1.w, pw1, G1, wv1, qv1, ok1);
-#ifdef R3DG_EXP_COUNT
-            {
-                const unsigned long long b0 = __ballot(ok0), b1 = __ballot(ok1);
-                if (l == 0) {
-                    R3DG_EXP_ADD(5, (b0 != 0ull ? 1 : 0) + (b1 != 0ull ? 1 : 0));
-                    R3DG_EXP_ADD(6, __builtin_popcountll(b0) + __builtin_popcountll(b1));
-                }
-            }
-#else
             (void)ok0;
             (void)ok1;
-#endif
             // every visited instance was blended by a pixel of this wave: one group row each; lane 0
             // also writes the row's bookkeeping into the image rows' pad columns (the flush reads it)
             {
@@ -848,57 +722,29 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
                 wr[0] = wv0;
                 wr[GRP * WQS] = qv0;
                 const uint32_t id0 = __builtin_amdgcn_readlane(row_l, j0);
-                if (lane0) {
-                    if constexpr (!R3DG_BWD_ORIGIN_MOMENTS) *reinterpret_cast<float2*>(wq + r * WQS + 64) = xy0;
-                    reinterpret_cast<uint32_t*>(wq)[(GRP + r) * WQS + 64] = id0;
-                }
+                if (lane0) reinterpret_cast<uint32_t*>(wq)[(GRP + r) * WQS + 64] = id0;
             }
             if (has1) {
                 float* wr = wq + (r + 1) * WQS + l;
                 wr[0] = wv1;
                 wr[GRP * WQS] = qv1;
                 const uint32_t id1 = __builtin_amdgcn_readlane(row_l, j1);
-                if (lane0) {
-                    if constexpr (!R3DG_BWD_ORIGIN_MOMENTS) *reinterpret_cast<float2*>(wq + (r + 1) * WQS + 64) = xy1;
-                    reinterpret_cast<uint32_t*>(wq)[(GRP + r + 1) * WQS + 64] = id1;
-                }
+                if (lane0) reinterpret_cast<uint32_t*>(wq)[(GRP + r + 1) * WQS + 64] = id1;
             }
             r += has1 ? 2 : 1;
             if (r > GRP - 2) {
-#ifdef R3DG_EXP_COUNT
-                const long long tf0 = wall_clock64();
-#endif
                 flush(r);
-#ifdef R3DG_EXP_COUNT
-                t_flush += wall_clock64() - tf0;
-#endif
                 r = 0;
             }
         }
         // the next batch's records have landed (this wave's DMA) and every wave is done with
         // this buffer before the next iteration's DMA overwrites it
-#ifdef R3DG_EXP_COUNT
-        const long long tw0 = wall_clock64();
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-#ifndef R3DG_EXP_NOBARRIER  // timing experiment only (results invalid): no cross-wave batch sync
         __syncthreads();
-#endif
-#ifdef R3DG_EXP_COUNT
-        t_wait += wall_clock64() - tw0;
-#endif
         buf ^= 1;
         gid_cur = gid_staged;
     }
     if (r > 0) flush(r);
-#ifdef R3DG_EXP_COUNT
-    if (l == 0) {
-        R3DG_EXP_ADD(2, t_wait);                    // batch-end DMA wait + barrier, per wave
-        R3DG_EXP_ADD(3, wall_clock64() - t_begin);  // batch loop total, per wave
-        R3DG_EXP_ADD(4, t_mask);                    // DMA issue + live masks, per wave
-        R3DG_EXP_ADD(7, t_flush);                   // in-loop flushes, per wave
-    }
-#endif
 }
 
 template <int SMAX>
@@ -1277,13 +1123,8 @@ hipError_t launch_sh_grad_views(int g0, int n, int deg, int M, int N, const floa
 // [S0, Sdx, Sdy, Sdxdx], lane NXC + 1 [Sdxdy, Sdydy]. Writes sums + g * RS = [X part (XW) |
 // dL/dmean2D x, y | dL/dconic x, y, z | dL/dopacity | 0, 0] (backward.cu:552-611 summed over the
 // pixels).
-#ifndef R3DG_ROWSUM_RPI
-#define R3DG_ROWSUM_RPI 4  // present rows loaded per iteration (independent float4 loads per lane;
-                           // measured at M1: 2 -> 0.230, 4 -> 0.206, 8 -> 0.215 ms)
-#endif
-#ifndef R3DG_ROWSUM_PF
-#define R3DG_ROWSUM_PF 1  // row-sum: next chunk's flag word prefetched
-#endif
+constexpr int kRowSumRPI = 4;  // present rows loaded per iteration (independent float4 loads per lane;
+                               // measured at M1: 2 -> 0.230, 4 -> 0.206, 8 -> 0.215 ms)
 
 template <int SMAX>
 __global__ void __launch_bounds__(256) row_sum_kernel(GatherBwdArgs a) {
@@ -1307,18 +1148,12 @@ __global__ void __launch_bounds__(256) row_sum_kernel(GatherBwdArgs a) {
         xy = a.means2D[g];
     }
     const bool mom = c >= NXC;                    // a moment lane (NXC, NXC + 1) or idle
-#if R3DG_ROWSUM_PF
     // the next chunk's flag word is loaded before this chunk's rows: one dependent round trip per
     // chunk instead of two
     uint32_t fw_next = (c < CH && c < n) ? a.flags[k0 + c] : 0u;
-#endif
     for (uint32_t kb = 0; kb < n; kb += CH) {
-#if R3DG_ROWSUM_PF
         const uint32_t fw = fw_next;
         fw_next = (c < CH && kb + CH + c < n) ? a.flags[k0 + kb + CH + c] : 0u;
-#else
-        const uint32_t fw = (c < CH && kb + c < n) ? a.flags[k0 + kb + c] : 0u;
-#endif
         uint32_t mask = ((fw & 0xffu) ? 1u : 0u) | ((fw & 0xff00u) ? 2u : 0u) | ((fw & 0xff0000u) ? 4u : 0u) |
                         ((fw & 0xff000000u) ? 8u : 0u);
         mask <<= 4 * (c & (CH - 1));
@@ -1326,9 +1161,9 @@ __global__ void __launch_bounds__(256) row_sum_kernel(GatherBwdArgs a) {
         for (int o = 1; o < LPG; o <<= 1) mask |= __shfl_xor(mask, o);
         const float* base = a.rows + (size_t)(k0 + kb) * 4 * RS;
         while (mask) {
-            float4 v[R3DG_ROWSUM_RPI];
+            float4 v[kRowSumRPI];
 #pragma unroll
-            for (int i = 0; i < R3DG_ROWSUM_RPI; ++i) {
+            for (int i = 0; i < kRowSumRPI; ++i) {
                 const int bit = mask ? __builtin_ctz(mask) : 0;
                 const bool has = mask != 0u;
                 const float4* row = reinterpret_cast<const float4*>(base + (size_t)bit * RS);
@@ -1337,12 +1172,12 @@ __global__ void __launch_bounds__(256) row_sum_kernel(GatherBwdArgs a) {
             }
             if (!mom) {
 #pragma unroll
-                for (int i = 0; i < R3DG_ROWSUM_RPI; ++i) {
+                for (int i = 0; i < kRowSumRPI; ++i) {
                     acc.x += v[i].x; acc.y += v[i].y; acc.z += v[i].z; acc.w += v[i].w;
                 }
             } else {
 #pragma unroll
-                for (int i = 0; i < R3DG_ROWSUM_RPI; ++i) {
+                for (int i = 0; i < kRowSumRPI; ++i) {
                     // the other moment column from the neighbouring lane (DPP quad_perm [1, 0, 3, 2])
                     const float4 vo = make_float4(dpp_mov<0xB1>(v[i].x), dpp_mov<0xB1>(v[i].y), dpp_mov<0xB1>(v[i].z),
                                                   dpp_mov<0xB1>(v[i].w));
@@ -1410,12 +1245,10 @@ __global__ void __launch_bounds__(256) gather_bwd_kernel(GatherBwdArgs a) {
             x[4 * q] = v.x; x[4 * q + 1] = v.y; x[4 * q + 2] = v.z; x[4 * q + 3] = v.w;
         }
         if (a.sums_moments) {
-            // the atomic flush summed the moments in double (render_bwd_glds_kernel): about the image
-            // origin (R3DG_BWD_ORIGIN_MOMENTS), expanded here about the mean (dx = mean - pixel), or
-            // about the mean already; dL/dmean2D, dL/dconic and dL/dopacity from them in double,
-            // rounded once
+            // the atomic flush summed the moments in double (render_bwd_glds_kernel) about the image
+            // origin: expanded here about the mean (dx = mean - pixel); dL/dmean2D, dL/dconic and
+            // dL/dopacity from them in double, rounded once
             const double2* md = reinterpret_cast<const double2*>(row + XW);
-#if R3DG_BWD_ORIGIN_MOMENTS
             double2 m0 = md[0], m1 = md[1], m2 = md[2];  // [G0, GX], [GY, GXX], [GXY, GYY]
             {
                 const float2 mu = a.means2D[g];
@@ -1428,9 +1261,6 @@ __global__ void __launch_bounds__(256) gather_bwd_kernel(GatherBwdArgs a) {
                 m1 = make_double2(sdy, sxx);
                 m2 = make_double2(sxy, syy);
             }
-#else
-            const double2 m0 = md[0], m1 = md[1], m2 = md[2];
-#endif
             const float4 co = a.conic_opacity[g];
             const double o = -0.5 * (double)co.w;
             x[XW + 0] = (float)(o * a.W * ((double)co.x * m0.y + (double)co.y * m1.x));

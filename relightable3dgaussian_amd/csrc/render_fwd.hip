@@ -25,9 +25,7 @@ namespace r3dg {
 R3DG_EXP_READER(r3dg_exp_counters_fwd)
 #endif
 
-#ifndef R3DG_FWD_WAVES
-#define R3DG_FWD_WAVES 8  // waves per SIMD the register allocation targets (SMAX <= 12): 64 VGPR
-#endif
+constexpr int kFwdWaves = 8;  // waves per SIMD the register allocation targets (SMAX <= 12): 64 VGPR
 
 // ---------------------------------------------------------------------------------------------
 // The default-shader blend (render records only): the records of batch b+1 are copied HBM -> LDS
@@ -37,19 +35,11 @@ R3DG_EXP_READER(r3dg_exp_counters_fwd)
 // own quadrant. Staging layout: column q (float4 q of the render record) of instance j at
 // [q * NB + j].
 // ---------------------------------------------------------------------------------------------
-#ifndef R3DG_FWD_TSIGN
-#define R3DG_FWD_TSIGN 1  // the pixel's stop kept as T's sign (no done mask); 0: a done mask (rounds 1-5)
-#endif
-#ifndef R3DG_FWD_SWALK
-#define R3DG_FWD_SWALK 1  // the pair loop's live-mask walk by s_ff1 + s_bitset0 (inline asm)
-#endif
-#ifndef R3DG_FWD_HALF
-#define R3DG_FWD_HALF 0  // 1: each 8x4 half of a wave's quadrant walks its own cull list (measured 3.4 % slower: profiles/r06/fwd_half_ab)
-#endif
-#ifndef R3DG_FWDG_NB
-#define R3DG_FWDG_NB 64  // instances per staged batch (two resident: 12.3 KB, 64 VGPRs -> 8 waves/SIMD;
-                         // 128: 24.6 KB -> 6 waves/SIMD, measured 0.480 vs 0.447 ms at M1)
-#endif
+// Measured and removed: a done mask instead of T's sign (rounds 1-5), the live-mask walk
+// in plain C++ instead of s_ff1 + s_bitset0, and a cull list per 8x4 half of a wave's quadrant
+// (3.4 % slower: profiles/r06/fwd_half_ab).
+constexpr int kFwdNB = 64;  // instances per staged batch (two resident: 12.3 KB, 64 VGPRs -> 8 waves/SIMD;
+                            // 128: 24.6 KB -> 6 waves/SIMD, measured 0.480 vs 0.447 ms at M1)
 
 // SHADER (non-default splat shaders, forward.cu:907-971): the splat shaders edit the shader colour
 // and the features after the render records were written (the records keep the caller's features:
@@ -59,9 +49,9 @@ R3DG_EXP_READER(r3dg_exp_counters_fwd)
 // same DMA staging, cull, step and contribution bits as the default path.
 template <int SMAX, bool SHADER>
 // (SMAX = 0 keeps the 6-wave target: at 8 the compiler spills 14 SGPRs)
-__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SMAX == 0 ? 6 : SMAX <= 12 ? R3DG_FWD_WAVES : 1)))
+__global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SMAX == 0 ? 6 : SMAX <= 12 ? kFwdWaves : 1)))
 render_fwd_glds_kernel(RenderFwdArgs a) {
-    constexpr int NB = R3DG_FWDG_NB;
+    constexpr int NB = kFwdNB;
     constexpr int NH = NB / 64;                // staged instances per lane
     constexpr int NA4 = (4 + SMAX + 3) / 4;    // float4 per attribute row
     constexpr int RF4 = 2 + NA4;               // float4 per render record
@@ -71,11 +61,7 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
     static_assert(NB == 64, "one 64-bit contribution word per wave and batch");
     // one LDS array: [2 staging buffers | 2 x 64 x 4 contribution flags (batch buffer, instance, wave)
     // | the tile's sorted Gaussian ids (fused sort)]; the fused sort's scratch aliases the staging
-#if R3DG_FWD_SORT_BUCKET
     using FusedSortLds = TileBucketSortLds<kFusedSortMax / kSortBT>;  // bucket sort | its radix fallback
-#else
-    using FusedSortLds = TileSortLds<kFusedSortMax / kSortBT>;
-#endif
     constexpr int SORT4 = (int)((sizeof(FusedSortLds) + 15) / 16);
     constexpr int STG = 2 * SBUF > SORT4 ? 2 * SBUF : SORT4;  // float4 of staging / sort scratch
     __shared__ float4 s_lds[STG + 64 + kFusedSortMax / 4];
@@ -98,7 +84,7 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
     // fused depth sort (block-uniform): the tile's (depth bits, id) pairs sorted in the prologue
     // (r3dg_tilesort.h), ids kept in LDS for the staging and written out for the backward; saves
     // the standalone sort launch. Here the sort's latency hides under the other resident workgroups
-    // and its instructions are what costs: a one-pass bucket sort (R3DG_FWD_SORT_BUCKET), 0.037 ms
+    // and its instructions are what costs: a one-pass bucket sort (sort_tile_bucket), 0.037 ms
     // less of this kernel at M1 than the radix sort's passes
     const bool fused = a.pairs != nullptr && n <= kFusedSortMax;
     if (fused && n > 0) {
@@ -111,7 +97,6 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
             keys[k] = kv.x;
             vals[k] = kv.y;
         }
-#if R3DG_FWD_SORT_BUCKET && !defined(R3DG_EXP_NOSORT)
         // the ids land in s_ids by final rank; the list for the backward is written from there,
         // consecutive lanes on consecutive positions
         sort_tile_bucket<IPT>(keys, vals, n, *reinterpret_cast<FusedSortLds*>(s_lds), s_ids);
@@ -121,34 +106,13 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
             const int i = t + k * kSortBT;
             if (i < n) a.point_list_out[range.x + i] = s_ids[i];
         }
-#else
-#ifndef R3DG_EXP_NOSORT  // timing experiment only (results invalid): the blend without the fused sort
-        if (n > 1) sort_pairs_chunk<IPT>(keys, vals, n, *reinterpret_cast<TileSortLds<IPT>*>(s_lds));
-#endif
-#pragma unroll
-        for (int k = 0; k < IPT; ++k) {
-            const int i = t * IPT + k;
-            if (i < n) {
-                s_ids[i] = vals[k];
-                a.point_list_out[range.x + i] = vals[k];
-            }
-        }
-        __syncthreads();
-#endif
     }
 
-#if R3DG_FWD_TSIGN
     // A pixel's stop is T's sign: the reference sets `done` when a contributing instance would take T
     // below 1e-4 and keeps T; here T becomes -|T| (one v_cndmask with source modifiers), every later
     // test_T = T (1 - alpha) < 0 stops again and leaves it there, and final_T is |T|. No separate
     // done mask, which the compiler moved between SGPR and VGPR form at every step.
     float T = inside ? 1.0f : -1.0f;
-#define R3DG_DONE (T < 0.0f)
-#else
-    bool done = !inside;
-    float T = 1.0f;
-#define R3DG_DONE done
-#endif
     uint32_t last = 0;
     float C[3] = {0.f, 0.f, 0.f}, F[SMAX > 0 ? SMAX : 1];
     float CS[SHADER ? 3 : 1];
@@ -226,7 +190,7 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
     for (; base < n; base += NB) {
         // batch `base` has landed (every wave waited for its own DMA) and nobody reads the other
         // buffer any more
-        const bool all_done = __syncthreads_count(R3DG_DONE) == kBlock;
+        const bool all_done = __syncthreads_count(T < 0.0f) == kBlock;
         // the previous batch's flags, before the DMA issue: folding them after wave 0's DMA issue
         // measured 0.556 vs 0.480 ms
         if (base > 0) write_bits(base - NB, NB, buf ^ 1);
@@ -237,20 +201,6 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
         }
         const float4* st = s_lds + buf * SBUF;
         const int cnt = min(NB, n - base);
-#if R3DG_FWD_HALF
-        // the exact cull per 8x4 half of the quadrant: one live mask per half
-        unsigned long long bt, bb;
-        {
-            bool mt = false, mb = false;
-            if (l < cnt) {
-                const float4 co = st[l], r1 = st[NB + l];
-                half_live(make_float2(r1.x, r1.y), co, uniform_f(qx0), uniform_f(qx0 + 7.0f), uniform_f(qy0),
-                          uniform_f(qy0 + 3.0f), uniform_f(qy0 + 4.0f), uniform_f(qy0 + 7.0f), a.cull, mt, mb);
-            }
-            bt = __ballot(mt);
-            bb = __ballot(mb);
-        }
-#else
         unsigned long long bits[NH];
 #pragma unroll
         for (int h = 0; h < NH; ++h) {
@@ -262,15 +212,10 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
             }
             bits[h] = __ballot(mine);
         }
-#endif
-        // j: the staged instance (R3DG_FWD_HALF: per lane, one per half of the wave)
+        // j: the staged instance
         auto step = [&](int j, bool live, float opacity, float power, float G) {
 #pragma clang fp contract(off)  // explicit FMAs only: both unrolled copies round alike
-#if R3DG_FWD_HALF
-            const int ju = j;
-#else
             const int ju = __builtin_amdgcn_readfirstlane(j);
-#endif
             float v[NA4 * 4];
 #pragma unroll
             for (int q = 0; q < NA4; ++q) {
@@ -279,32 +224,14 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
                 v[4 * q] = r.x; v[4 * q + 1] = r.y; v[4 * q + 2] = r.z; v[4 * q + 3] = r.w;
             }
             const float alpha = fminf(0.99f, opacity * G);  // bit-identical to the oracle
-#if R3DG_FWD_TSIGN
             const bool contrib = live && !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
             const float test_T = T * (1.0f - alpha);
             const bool stop = test_T < 0.0001f;  // also every step after the pixel's stop (T < 0)
             if (contrib && stop) T = -fabsf(T);
-#else
-            const bool contrib = live && !done && !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
-            const float test_T = T * (1.0f - alpha);
-            const bool stop = test_T < 0.0001f;
-            done = done || (contrib && stop);
-#endif
-#ifdef R3DG_EXP_COUNT
-            {
-                const unsigned long long acc_b = __ballot(contrib && !stop);
-                if (l == 0) {
-                    R3DG_EXP_ADD(4, __builtin_popcountll(acc_b));
-                    R3DG_EXP_ADD(5, acc_b != 0ull ? 1 : 0);
-                }
-            }
-#endif
             if (contrib && !stop) {
-#if R3DG_ATTR_B128
                 // the unused pad channel kept live: one ds_read_b128 (4 LDS-array cycles) for the
                 // last row instead of a ds_read_b96 (8)
                 if constexpr ((4 + SMAX) % 4 != 0) asm volatile("" ::"v"(v[NA4 * 4 - 1]));
-#endif
                 const float wgt = alpha * T;
                 C[0] = __builtin_fmaf(v[0], wgt, C[0]);
                 C[1] = __builtin_fmaf(v[1], wgt, C[1]);
@@ -324,81 +251,35 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
                 s_cf[(buf * 64 + ju) * 8 + 2 * w + (l >> 5)] = 1;  // every accumulating lane of a half: one byte
             }
         };
-#if R3DG_FWD_HALF
-        // Each half of the wave walks its own live list, two instances per iteration; a half whose
-        // 32 pixels are all done, or whose list ran out, idles (live = false) while the other walks on.
-        const bool top = l < 32;
-        {
-            const unsigned long long nd = __ballot(!R3DG_DONE);
-            if ((uint32_t)nd == 0u) bt = 0ull;
-            if ((uint32_t)(nd >> 32) == 0u) bb = 0ull;
-        }
-        while (bt | bb) {
-            const int t0 = bt ? (int)__builtin_ctzll(bt) : -1;
-            bt &= bt - 1;
-            const int t1 = bt ? (int)__builtin_ctzll(bt) : -1;
-            bt &= bt - 1;
-            const int b0 = bb ? (int)__builtin_ctzll(bb) : -1;
-            bb &= bb - 1;
-            const int b1 = bb ? (int)__builtin_ctzll(bb) : -1;
-            bb &= bb - 1;
-            const int s0 = top ? t0 : b0, s1 = top ? t1 : b1;
-            const bool live0 = s0 >= 0, live1 = s1 >= 0;
-            const int j0 = live0 ? s0 : 0, j1 = live1 ? s1 : j0;  // valid staging slots either way
-            const float4 co0 = st[j0], co1 = st[j1];
-            const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + j0);
-            const float2 xy1 = *reinterpret_cast<const float2*>(st + NB + j1);
-            const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
-            const float pw1 = gauss_power(co1, xy1.x - pfx, xy1.y - pfy);
-            const f32x2 G = {blend_expf(pw0), blend_expf(pw1)};
-            step(j0, live0, co0.w, pw0, G.x);
-            step(j1, live1, co1.w, pw1, G.y);
-            const unsigned long long nd = __ballot(!R3DG_DONE);
-            if ((uint32_t)nd == 0u) bt = 0ull;
-            if ((uint32_t)(nd >> 32) == 0u) bb = 0ull;
-        }
-#else
         static_assert(NH == 1, "one 64-bit live mask per batch");
         unsigned long long b = bits[0];
         if (l == 0) R3DG_EXP_ADD(3, __builtin_popcountll(b));
-        if (__ballot(!R3DG_DONE) == 0ull) b = 0ull;  // (every pixel of the wave stopped)
-        {
-            constexpr int h = 0;
-            while (b) {
-#if R3DG_FWD_SWALK
-                // the pair from the live mask by s_ff1 + s_bitset0 (s_ff1 of an empty mask is -1, whose
-                // s_bitset0 clears the already clear bit 63): 4 scalar ops for what b &= b - 1 twice,
-                // two s_ff1 and their selects took 11
-                int j0, j1;
-                asm("s_ff1_i32_b64 %0, %2\n\ts_bitset0_b64 %2, %0\n\ts_ff1_i32_b64 %1, %2\n\ts_bitset0_b64 %2, %1"
-                    : "=&s"(j0), "=&s"(j1), "+s"(b));
-                const bool has1 = j1 >= 0;
-                j1 = has1 ? j1 : j0;
-#else
-                const int j0 = h * 64 + (int)__builtin_ctzll(b);
-                b &= b - 1;
-                const bool has1 = b != 0ull;
-                const int j1 = has1 ? h * 64 + (int)__builtin_ctzll(b) : j0;
-                b &= b - 1;
-#endif
-                const int u0 = __builtin_amdgcn_readfirstlane(j0), u1 = __builtin_amdgcn_readfirstlane(j1);
-                const float4 co0 = st[u0], co1 = st[u1];
-                const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + u0);
-                const float2 xy1 = *reinterpret_cast<const float2*>(st + NB + u1);
-                const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
-                const float pw1 = gauss_power(co1, xy1.x - pfx, xy1.y - pfy);
-                // two scalar exp chains, interleaved by the scheduler (the packed pair, r3dg_expf2,
-                // needs an s_nop between its dependent v_pk_fma_f32: 0.3 % slower at M1)
-                const f32x2 G = {blend_expf(pw0), blend_expf(pw1)};
-                step(j0, true, co0.w, pw0, G.x);
-                step(j1, has1, co1.w, pw1, G.y);
-                if (l == 0) R3DG_EXP_ADD(2, has1 ? 2 : 1);
-                // converged here: a uniform exit (testing every 2 or 4 iterations instead, which
-                // drops ~10 scalar instructions per iteration, measured no faster in round 3)
-                if (__ballot(!R3DG_DONE) == 0ull) break;
-            }
+        if (__ballot(!(T < 0.0f)) == 0ull) b = 0ull;  // (every pixel of the wave stopped)
+        while (b) {
+            // the pair from the live mask by s_ff1 + s_bitset0 (s_ff1 of an empty mask is -1, whose
+            // s_bitset0 clears the already clear bit 63): 4 scalar ops for what b &= b - 1 twice,
+            // two s_ff1 and their selects took 11
+            int j0, j1;
+            asm("s_ff1_i32_b64 %0, %2\n\ts_bitset0_b64 %2, %0\n\ts_ff1_i32_b64 %1, %2\n\ts_bitset0_b64 %2, %1"
+                : "=&s"(j0), "=&s"(j1), "+s"(b));
+            const bool has1 = j1 >= 0;
+            j1 = has1 ? j1 : j0;
+            const int u0 = __builtin_amdgcn_readfirstlane(j0), u1 = __builtin_amdgcn_readfirstlane(j1);
+            const float4 co0 = st[u0], co1 = st[u1];
+            const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + u0);
+            const float2 xy1 = *reinterpret_cast<const float2*>(st + NB + u1);
+            const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
+            const float pw1 = gauss_power(co1, xy1.x - pfx, xy1.y - pfy);
+            // two scalar exp chains, interleaved by the scheduler (the packed pair, r3dg_expf2,
+            // needs an s_nop between its dependent v_pk_fma_f32: 0.3 % slower at M1)
+            const f32x2 G = {r3dg_expf(pw0), r3dg_expf(pw1)};
+            step(j0, true, co0.w, pw0, G.x);
+            step(j1, has1, co1.w, pw1, G.y);
+            if (l == 0) R3DG_EXP_ADD(2, has1 ? 2 : 1);
+            // converged here: a uniform exit (testing every 2 or 4 iterations instead, which
+            // drops ~10 scalar instructions per iteration, measured no faster in round 3)
+            if (__ballot(!(T < 0.0f)) == 0ull) break;
         }
-#endif
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         buf ^= 1;
     }
@@ -423,10 +304,7 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
         const uint32_t z0 = (uint32_t)tile * a.zero_chunk, z1 = min(z0 + a.zero_chunk, a.zero_n4);
         for (uint32_t i = z0 + (uint32_t)t; i < z1; i += kBlock) a.zero_sums[i] = make_float4(0.f, 0.f, 0.f, 0.f);
     }
-#undef R3DG_DONE
-#if R3DG_FWD_TSIGN
     T = fabsf(T);
-#endif
     if (inside) {
         const int pix = py * a.W + px;
         a.final_T[pix] = T;
@@ -572,7 +450,7 @@ __global__ void __launch_bounds__(kBlock) intermediate_glds_kernel(IntermediateA
             const float2 xy1 = *reinterpret_cast<const float2*>(st + NB + u1);
             const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
             const float pw1 = gauss_power(co1, xy1.x - pfx, xy1.y - pfy);
-            const f32x2 G = {blend_expf(pw0), blend_expf(pw1)};  // scalar chains, as the default blend
+            const f32x2 G = {r3dg_expf(pw0), r3dg_expf(pw1)};  // scalar chains, as the default blend
             step(j0, true, pw0, G.x);
             step(j1, has1, pw1, G.y);
         }
@@ -614,11 +492,8 @@ __device__ __forceinline__ float3 surface_point(const XyzNormalArgs& a, int x, i
     return make_float3(((float)x - a.cx) / a.focal_x * d, ((float)y - a.cy) / a.focal_y * d, d);
 }
 
-// One workgroup per 16 x (16 XYZ_R) pixels (XYZ_R tile rows: the halo and the launch's latency
+// One workgroup per 16 x (16 kXyzRows) pixels (kXyzRows tile rows: the halo and the launch's latency
 // amortised over more pixels); thread t handles pixel column t & 15 of rows t >> 4, + 16, ...
-#ifndef R3DG_XYZ_R
-#define R3DG_XYZ_R 4
-#endif
 // The backward's launch order from the forward's per-tile work counts (RenderFwdArgs::bwd_work): a
 // bucket sort by work / 4 (capped), descending, as the binning's instance-count order
 // (preprocess.hip tile_order_block). The forward counted the buckets and gave every tile its rank in
@@ -686,7 +561,7 @@ __global__ void __launch_bounds__(256) xyz_normal_kernel(XyzNormalArgs a) {
     // the kernel's last pixel blocks; as a last grid column they lengthened it by ~4 us)
     // the block's 18 x (16 R + 2) neighbourhood (edge-clamped) of surface points, each evaluated
     // once into LDS instead of nine times per pixel (the order workgroups use the same array)
-    constexpr int R = R3DG_XYZ_R, HW_ = 18, HH = 16 * R + 2;
+    constexpr int R = kXyzRows, HW_ = 18, HH = 16 * R + 2;
     static_assert(3 * HW_ * HH >= kWorkBuckets + 4, "the order's LDS fits the halo array");
     __shared__ float sp[3][HW_ * HH];
     const int nord = a.bwd_order ? kOrderSlices : 0;
