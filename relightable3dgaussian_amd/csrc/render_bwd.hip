@@ -435,7 +435,6 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
     const int max_last = block_max_last(wmax, s_max_last);
     const int RS = a.RS;
     const int nch = l & 15;
-    const bool lane0 = l == 0;
     const float4* st = stage;  // staging buffer of the current batch
 
     auto step = [&](int j, int p, bool live, float opacity, float power, float G, float& wv, float& qv,
@@ -558,9 +557,10 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
             accY = __builtin_amdgcn_mfma_f32_16x16x32_bf16(m, yb[b], accY, 0, 0, 0);
             accY = __builtin_amdgcn_mfma_f32_16x16x32_bf16(o, yb[b], accY, 0, 0, 0);
         }
-        // Group row r's bookkeeping sits in the pad column of its w|q image (written by lane 0 at the
-        // visit): its Gaussian (ATOM) or partial row (4 * slot + quadrant) at q row r, column 64. Lane
-        // group g handles D rows 4g + i of accumulator element i: one broadcast LDS read per row.
+        // Group row r's bookkeeping sits in the pad column of its w|q image (written at the visit by
+        // the lane that staged the instance): its Gaussian (ATOM) or partial row (4 * slot + quadrant)
+        // at q row r, column 64. Lane group g handles D rows 4g + i of accumulator element i: one
+        // broadcast LDS read per row.
         uint32_t rid[4];
 #pragma unroll
         for (int i = 0; i < 4; ++i)
@@ -715,21 +715,21 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
             step(j1, hi - 1 - j1, has1, co1.w, pw1, G1, wv1, qv1, ok1);
             (void)ok0;
             (void)ok1;
-            // every visited instance was blended by a pixel of this wave: one group row each; lane 0
-            // also writes the row's bookkeeping into the image rows' pad columns (the flush reads it)
+            // every visited instance was blended by a pixel of this wave: one group row each; the
+            // lane that holds the instance's row id (lane j of the batch) also writes it into the image
+            // row's pad column (the flush reads it): one compare per visit. Handing it to lane 0 with
+            // a v_readlane and a copy back to a VGPR measured 2.4 % slower
             {
                 float* wr = wq + r * WQS + l;
                 wr[0] = wv0;
                 wr[GRP * WQS] = qv0;
-                const uint32_t id0 = __builtin_amdgcn_readlane(row_l, j0);
-                if (lane0) reinterpret_cast<uint32_t*>(wq)[(GRP + r) * WQS + 64] = id0;
+                if (l == j0) reinterpret_cast<uint32_t*>(wq)[(GRP + r) * WQS + 64] = row_l;
             }
             if (has1) {
                 float* wr = wq + (r + 1) * WQS + l;
                 wr[0] = wv1;
                 wr[GRP * WQS] = qv1;
-                const uint32_t id1 = __builtin_amdgcn_readlane(row_l, j1);
-                if (lane0) reinterpret_cast<uint32_t*>(wq)[(GRP + r + 1) * WQS + 64] = id1;
+                if (l == j1) reinterpret_cast<uint32_t*>(wq)[(GRP + r + 1) * WQS + 64] = row_l;
             }
             r += has1 ? 2 : 1;
             if (r > GRP - 2) {
