@@ -535,6 +535,86 @@ int r3dg_image_loss_backward(int planes, int H, int W, const float* img, int64_t
 /* the 11 window weights the kernels use: gaussian(11, 1.5) of utils/loss_utils.py:19-21 in f32 (host memory) */
 const float* r3dg_image_loss_window(void);
 
+/* ---- image-space regularisers (reference: gaussian_renderer/neilf.py:233-321) ---------------- */
+
+/* The eight image terms of calculate_loss beside L1 + SSIM, in fused form: one forward launch pair and
+ * one backward launch for whichever are enabled. A map is n planes of [H, W]; element (c, y, x) is
+ * ptr[c * plane_stride + y * row_stride + x * px_stride] (strides in elements): CHW is (H*W, W, 1), a
+ * rasterizer feature group [H*W, n] is (1, W*n, n). Both run the same code and give the same bits.
+ *
+ * Rendered maps (differentiable): opacity 1, depth 1, normal 3, base_color 3, roughness 1, metallic 1
+ * planes; pseudo_normal 3 (the reference detaches it: no gradient). Targets: gt_image 3, gt_depth 1,
+ * image_mask 1 (ptr NULL: 1 everywhere, scene/cameras.py:55), mvs_normal 3. With m the mask value,
+ * N = H * W and all arithmetic in f32 with the accurate expf / logf:
+ *   DEPTH (neilf.py:233-241)  over the pixels where (m != 0) == (gt_depth > 0):
+ *       sum |depth - gt_depth| / their count; no such pixel: 0 / 0 = NaN, as F.l1_loss of an empty
+ *       selection, with an all-zero gradient. The count is an exact integer.
+ *   MASK_ENTROPY (243-248)  o' = clamp(opacity, (float)1e-6, (float)(1 - 1e-6));
+ *       -sum (m log o' + (1 - m) log(1 - o')) / N; gradient only where opacity is within the bounds
+ *       (inclusive), as torch's clamp. A NaN opacity stays NaN through the clamp, as in torch: the term
+ *       is NaN and that pixel's gradient 0.
+ *   NORMAL_RENDER_DEPTH (250-256)  sum (normal m - pseudo_normal m)^2 / 3N.
+ *   NORMAL_MVS_DEPTH (258-276)  the same with dm = (gt_depth > 0) and mvs_normal (the caller supplies
+ *       mvs_normal; the kornia branch is not part of this).
+ *   BASE_COLOR (285-303)  gm = gt_image m, v = max over channels of gm, w = 1 / (1 + exp(-5 (v - 0.5))),
+ *       t = w gm^2 + (1 - w)(1 - (1 - gm)^2); sum |t - base_color| / 3N.
+ *   BASE_COLOR_SMOOTH, METALLIC_SMOOTH, ROUGHNESS_SMOOTH (305-321; utils/loss_utils.py:65-96
+ *       bilateral_smooth_loss)  G(x) = |Sobel_x| + |Sobel_y| of the channel mean of x with zero "same"
+ *       padding; sum G(data) exp(-G(gt_image)) m / N. A 3x3 neighbourhood of equal means gives
+ *       exactly 0 and no gradient.
+ * sign(0) = 0 wherever torch has it (abs, l1_loss). The two normal terms add into one normal
+ * gradient, the guide and the smoothness term into one base_color gradient.
+ *
+ * forward: values f32 [R3DG_REG_TERMS] = each enabled term's value (a disabled term's slot is 0),
+ * depth_count int32 [1] = the depth term's selected pixels. Tile partials are added in a fixed order
+ * in f64: two calls give the same bits. Scratch from scratch_alloc: 36 B per 16x16 tile.
+ *
+ * backward: for every map an enabled term reaches and whose pointer in `out` is not NULL, writes
+ *   scale[0] * sum over its terms of weights[term] * d(term value)/d(map)
+ * once (overwrite), addressed with that map's own strides. weights f32 [R3DG_REG_TERMS] and the
+ * optional scale f32 [1] (NULL: 1) are device arrays: lambda and the upstream gradient, or their
+ * product in weights. scale multiplies last, so a loss scaled by k gives fl(k * gradient) exactly.
+ * depth_count is the forward's. Nothing is saved by the forward; both calls take the same inputs.
+ *
+ * Checked in this order, before any device work. (1) A NULL or wrongly sized struct (struct_size other
+ * than sizeof as declared here), negative H / W, unknown bits in terms: R3DG_ERR_ARG. (2) H or W == 0,
+ * or no term enabled: R3DG_OK, nothing launched or allocated, whatever the remaining arguments are (so
+ * an image beyond int32 with no term enabled is R3DG_OK). (3) H*W > INT32_MAX, a NULL map that an
+ * enabled term needs, a NULL values / depth_count / weights or a NULL scratch_alloc: R3DG_ERR_ARG.
+ * Everything is enqueued on stream, with no host synchronisation. */
+enum {
+    R3DG_REG_DEPTH = 0,               /* tb_dict "loss_depth" */
+    R3DG_REG_MASK_ENTROPY = 1,        /* "loss_mask_entropy" */
+    R3DG_REG_NORMAL_RENDER_DEPTH = 2, /* "loss_normal_render_depth" */
+    R3DG_REG_NORMAL_MVS_DEPTH = 3,    /* "loss_normal_mvs_depth" */
+    R3DG_REG_BASE_COLOR = 4,          /* "loss_base_color" */
+    R3DG_REG_BASE_COLOR_SMOOTH = 5,   /* "loss_base_color_smooth" */
+    R3DG_REG_METALLIC_SMOOTH = 6,     /* "loss_metallic_smooth" */
+    R3DG_REG_ROUGHNESS_SMOOTH = 7,    /* "loss_roughness_smooth" */
+    R3DG_REG_TERMS = 8
+};
+typedef struct r3dg_map {
+    const float* ptr; /* NULL: absent */
+    int64_t plane_stride, row_stride, px_stride;
+} r3dg_map;
+typedef struct r3dg_reg_loss_inputs {
+    size_t struct_size; /* sizeof(r3dg_reg_loss_inputs) (checked) */
+    int H, W;
+    unsigned terms;     /* bit (1 << R3DG_REG_*) set: the term is evaluated */
+    r3dg_map opacity, depth, normal, pseudo_normal, base_color, roughness, metallic; /* rendered */
+    r3dg_map gt_image, gt_depth, image_mask, mvs_normal;                             /* targets */
+} r3dg_reg_loss_inputs;
+typedef struct r3dg_reg_loss_grads {
+    size_t struct_size; /* sizeof(r3dg_reg_loss_grads) (checked) */
+    float *opacity, *depth, *normal, *base_color, *roughness, *metallic; /* NULL: not wanted */
+} r3dg_reg_loss_grads;
+int r3dg_reg_loss_forward(const r3dg_reg_loss_inputs* in, float* values /* [R3DG_REG_TERMS] */,
+                          int32_t* depth_count /* [1] */, r3dg_alloc_fn scratch_alloc, void* scratch_ctx,
+                          r3dg_stream_t stream);
+int r3dg_reg_loss_backward(const r3dg_reg_loss_inputs* in, const int32_t* depth_count,
+                           const float* weights /* [R3DG_REG_TERMS] */, const float* scale /* [1] or NULL */,
+                           const r3dg_reg_loss_grads* out, r3dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -26,7 +26,7 @@ ROCM = os.environ.get("ROCM_PATH", "/opt/rocm")
 HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
 HIP_SOURCES = ["preprocess.hip", "render_fwd.hip", "render_bwd.hip", "brdf.hip", "shaders.hip", "rasterizer.hip",
-               "optim.hip", "bvh.hip", "knn.hip", "loss.hip"]
+               "optim.hip", "bvh.hip", "knn.hip", "loss.hip", "reg_loss.hip"]
 HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-result",
              "-munsafe-fp-atomics", f"-I{INC}", f"-I{CSRC}"]
 # the key path (projection, radius, rect) must not contract a*b+c into fma: see preprocess.hip
@@ -42,8 +42,11 @@ HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-W
 # loss.hip: the per-pixel SSIM arithmetic rounds every operation, as the reference's tensor operations do, so
 # that identical images give ssim_map == 1 and a gradient of exactly 0 (a contracted a*b+c breaks the
 # cancellation: 1.2e-4 of a pixel's share measured); its filter loops call fmaf themselves
+# reg_loss.hip: the two sides of a Sobel difference are added in one order and must stay equal for equal
+# means (a contracted 2*b+c on one side only breaks the exact zero); the upstream scale multiplies last
 PER_FILE_FLAGS = {"preprocess.hip": ["-ffp-contract=off"], "bvh.hip": ["-ffp-contract=off"],
                   "knn.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
+                  "reg_loss.hip": ["-ffp-contract=off"],
                   "brdf.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],
                   "render_bwd.hip": ["-fno-slp-vectorize", "-mllvm", "-amdgpu-sched-strategy=max-memory-clause"],
                   "render_fwd.hip": ["-fno-slp-vectorize"]}

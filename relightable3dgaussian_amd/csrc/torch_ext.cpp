@@ -902,6 +902,122 @@ torch::Tensor image_loss_backward(const torch::Tensor& img, const torch::Tensor&
     return out;
 }
 
+// ---- image-space regularisers (neilf.py:233-321; csrc/reg_loss.hip) -------------------------------
+
+// The eleven maps in the order of r3dg_reg_loss_inputs: opacity, depth, normal, pseudo_normal, base_color,
+// roughness, metallic (rendered: [n,H,W], or the rasterizer's [H,W,n] with hwc), then gt_image, gt_depth,
+// image_mask, mvs_normal (always [n,H,W]). None is absent. The checked, contiguous tensors and the struct.
+struct RegInputs {
+    std::vector<torch::Tensor> keep;
+    r3dg_reg_loss_inputs in;
+    torch::Device dev{torch::kCPU};
+};
+constexpr int kRegMaps = 11, kRegRendered = 7;
+const int kRegPlanes[kRegMaps] = {1, 1, 3, 3, 3, 1, 1, 3, 1, 1, 3};
+const char* const kRegNames[kRegMaps] = {"opacity", "depth", "normal", "pseudo_normal", "base_color", "roughness",
+                                         "metallic", "gt_image", "gt_depth", "image_mask", "mvs_normal"};
+RegInputs reg_inputs(const std::vector<std::optional<torch::Tensor>>& maps, int64_t H, int64_t W, int64_t terms,
+                     bool hwc, const char* what) {
+    TORCH_CHECK((int64_t)maps.size() == kRegMaps, what, ": ", kRegMaps, " maps (or None) expected");
+    TORCH_CHECK(H >= 0 && W >= 0 && H * W <= (int64_t)INT32_MAX, what, ": H, W >= 0 and H * W within int32 expected");
+    TORCH_CHECK(terms >= 0 && terms < (1 << R3DG_REG_TERMS), what, ": unknown bits in terms");
+    RegInputs r;
+    r.keep.resize(kRegMaps);
+    r.in = r3dg_reg_loss_inputs{};
+    r.in.struct_size = sizeof(r3dg_reg_loss_inputs);
+    r.in.H = (int)H, r.in.W = (int)W, r.in.terms = (unsigned)terms;
+    r3dg_map* dst[kRegMaps] = {&r.in.opacity, &r.in.depth, &r.in.normal, &r.in.pseudo_normal, &r.in.base_color,
+                               &r.in.roughness, &r.in.metallic, &r.in.gt_image, &r.in.gt_depth, &r.in.image_mask,
+                               &r.in.mvs_normal};
+    bool have = false;
+    for (int i = 0; i < kRegMaps; ++i) {
+        if (!maps[i]) continue;
+        const torch::Tensor& t = *maps[i];
+        const int64_t n = kRegPlanes[i];
+        TORCH_CHECK(t.scalar_type() == torch::kFloat32, what, ": ", kRegNames[i], ": expected float32");
+        const bool pixel_major = hwc && i < kRegRendered;
+        if (pixel_major) {
+            TORCH_CHECK(t.dim() == 3 && t.size(0) == H && t.size(1) == W && t.size(2) == n, what, ": shape mismatch: ",
+                        kRegNames[i], " [H,W,", n, "] expected, got ", t.sizes());
+        } else {
+            TORCH_CHECK(t.dim() == 3 && t.size(0) == n && t.size(1) == H && t.size(2) == W, what, ": shape mismatch: ",
+                        kRegNames[i], " [", n, ",H,W] expected, got ", t.sizes());
+        }
+        TORCH_CHECK(t.is_cuda(), what, ": ", kRegNames[i], ": expected a GPU tensor (this build has no CPU path)");
+        if (!have) r.dev = t.device(), have = true;
+        TORCH_CHECK(t.device() == r.dev, what, ": ", kRegNames[i], ": maps on different devices");
+        r.keep[i] = t.contiguous();
+        if (t.numel() == 0) continue;
+        *dst[i] = pixel_major ? r3dg_map{r.keep[i].data_ptr<float>(), 1, W * n, n}
+                              : r3dg_map{r.keep[i].data_ptr<float>(), H * W, W, 1};
+    }
+    TORCH_CHECK(have, what, ": no map given");
+    return r;
+}
+
+// -> (values f32 [8]: each enabled term's value under its R3DG_REG_* index, 0 for a disabled one;
+//     depth_count int32 [1]: the pixels the depth term selected)
+std::tuple<torch::Tensor, torch::Tensor> reg_loss_forward(const std::vector<std::optional<torch::Tensor>>& maps,
+                                                          int64_t H, int64_t W, int64_t terms, bool hwc) {
+    auto a = reg_inputs(maps, H, W, terms, hwc, "reg_loss_forward");
+    const c10::OptionalDeviceGuard guard(a.dev);
+    const auto fopt = torch::TensorOptions().dtype(torch::kFloat32).device(a.dev);
+    // with work to do the finishing kernel writes every slot (0 for a disabled term)
+    const bool work = H * W != 0 && terms != 0;
+    auto values = work ? torch::empty({R3DG_REG_TERMS}, fopt) : torch::zeros({R3DG_REG_TERMS}, fopt);
+    auto count = work ? torch::empty({1}, fopt.dtype(torch::kInt32)) : torch::zeros({1}, fopt.dtype(torch::kInt32));
+    TensorAlloc scratch{fopt.dtype(torch::kUInt8), {}};
+    check(r3dg_reg_loss_forward(&a.in, values.data_ptr<float>(), count.data_ptr<int32_t>(), tensor_alloc, &scratch,
+                                stream_of(a.dev)),
+          "reg_loss_forward");
+    return {values, count};
+}
+
+// -> the gradients of opacity, depth, normal, base_color, roughness, metallic, each laid out like its map, or
+// None where `want` (a bit per map, in this order) is clear or no enabled term reaches the map
+std::vector<std::optional<torch::Tensor>> reg_loss_backward(const std::vector<std::optional<torch::Tensor>>& maps,
+                                                            int64_t H, int64_t W, int64_t terms, bool hwc,
+                                                            const torch::Tensor& depth_count,
+                                                            const torch::Tensor& weights,
+                                                            const std::optional<torch::Tensor>& scale, int64_t want) {
+    auto a = reg_inputs(maps, H, W, terms, hwc, "reg_loss_backward");
+    TORCH_CHECK(depth_count.is_cuda() && depth_count.device() == a.dev && depth_count.scalar_type() == torch::kInt32 &&
+                    depth_count.numel() == 1,
+                "reg_loss_backward: depth_count int32 [1] from reg_loss_forward expected");
+    TORCH_CHECK(weights.is_cuda() && weights.device() == a.dev && weights.scalar_type() == torch::kFloat32 &&
+                    weights.numel() == R3DG_REG_TERMS,
+                "reg_loss_backward: weights float32 [8] on the maps' device expected");
+    TORCH_CHECK(!scale || (scale->is_cuda() && scale->device() == a.dev && scale->scalar_type() == torch::kFloat32 &&
+                           scale->numel() == 1),
+                "reg_loss_backward: scale float32 [1] on the maps' device expected");
+    const auto w = weights.contiguous(), cnt = depth_count.contiguous();
+    const auto sc = scale ? scale->contiguous() : torch::Tensor();
+    const c10::OptionalDeviceGuard guard(a.dev);
+    const unsigned t = (unsigned)terms;
+    auto bit = [&](int k) { return (t >> k & 1u) != 0; };
+    // the map (index into maps) and whether an enabled term reaches it, in the order of the result
+    const int src[6] = {0, 1, 2, 4, 5, 6};
+    const bool reached[6] = {bit(R3DG_REG_MASK_ENTROPY),
+                             bit(R3DG_REG_DEPTH),
+                             bit(R3DG_REG_NORMAL_RENDER_DEPTH) || bit(R3DG_REG_NORMAL_MVS_DEPTH),
+                             bit(R3DG_REG_BASE_COLOR) || bit(R3DG_REG_BASE_COLOR_SMOOTH),
+                             bit(R3DG_REG_ROUGHNESS_SMOOTH),
+                             bit(R3DG_REG_METALLIC_SMOOTH)};
+    std::vector<std::optional<torch::Tensor>> out(6);
+    r3dg_reg_loss_grads g{};
+    g.struct_size = sizeof(r3dg_reg_loss_grads);
+    float** dst[6] = {&g.opacity, &g.depth, &g.normal, &g.base_color, &g.roughness, &g.metallic};
+    for (int i = 0; i < 6; ++i) {
+        if (!(want >> i & 1) || !reached[i] || !a.keep[src[i]].defined()) continue;
+        out[i] = torch::empty_like(a.keep[src[i]]);
+        if (out[i]->numel()) *dst[i] = out[i]->data_ptr<float>();
+    }
+    check(r3dg_reg_loss_backward(&a.in, cnt.data_ptr<int32_t>(), w.data_ptr<float>(),
+                                 scale ? sc.data_ptr<float>() : nullptr, &g, stream_of(a.dev)),
+          "reg_loss_backward");
+    return out;
+}
+
 // trace_bvh_opacity (bvh/src/bvh.cu:87-117): outputs shaped like rays_o without its last axis
 std::tuple<torch::Tensor, torch::Tensor> trace_bvh_opacity(const torch::Tensor& nodes, const torch::Tensor& aabbs,
                                                            const torch::Tensor& rays_o, const torch::Tensor& rays_d,
@@ -1062,6 +1178,12 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
           py::arg("need_grad"));
     m.def("image_loss_backward", &image_loss_backward, py::arg("img"), py::arg("gt"), py::arg("hwc"),
           py::arg("dmaps"), py::arg("w_ssim"), py::arg("w_abs"), py::arg("scale") = py::none());
+    // the fused depth / mask / normal / base-colour / smoothness terms (relightable3dgaussian_amd/loss.py)
+    m.def("reg_loss_forward", &reg_loss_forward, py::arg("maps"), py::arg("H"), py::arg("W"), py::arg("terms"),
+          py::arg("hwc"));
+    m.def("reg_loss_backward", &reg_loss_backward, py::arg("maps"), py::arg("H"), py::arg("W"), py::arg("terms"),
+          py::arg("hwc"), py::arg("depth_count"), py::arg("weights"), py::arg("scale") = py::none(),
+          py::arg("want") = 63);
     m.def("image_loss_window", []() {
         const float* w = r3dg_image_loss_window();
         return std::vector<float>(w, w + 11);
