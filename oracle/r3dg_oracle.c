@@ -1247,7 +1247,11 @@ void oracle_render_equation_backward(int P, int S_inc, int S_dir, int S_vis, con
             /* clamp checks after fmaxf never fire (render_equation.cu:440-449, bug-compatible) */
             for (int i = 0; i < S_dir; ++i)
                 for (int c = 0; c < 3; ++c) ddir_acc[i * 3 + c] += (double)dglob[c] * (double)coef[i];
-            for (int i = 0; i < S_dir; ++i) /* loop bound S_direct, render_equation.cu:450 */
+            /* the reference's loop bound is S_direct (render_equation.cu:450), which with
+             * S_incident < S_direct runs past the Gaussian's own row: bounded by both widths, as
+             * brdf.hip's n_inc_upd (coefficients i >= min(S_direct, S_incident) get no gradient) */
+            const int n_inc_upd = S_dir < S_inc ? S_dir : S_inc;
+            for (int i = 0; i < n_inc_upd; ++i)
                 for (int c = 0; c < 3; ++c)
                     d_inc[((size_t)idx * S_inc + i) * 3 + c] = fmaf(dli[c], coef[i], d_inc[((size_t)idx * S_inc + i) * 3 + c]);
             for (int c = 0; c < 3; ++c) {

@@ -9,7 +9,8 @@
 // all per-Gaussian gradient accumulators in registers; the environment SH (same for every
 // Gaussian) is read through the scalar path. The backward is bug-compatible with the
 // reference kernel (ReLU/clamp gradients never zeroed, dL_dn_d_i overwritten, no projection
-// term for the half-vector normalisation, dL_dincidents_shs bounded by S_direct) EXCEPT the
+// term for the half-vector normalisation, dL_dincidents_shs updated for the first S_direct
+// coefficients only -- capped at S_incident, where the reference would leave the row) EXCEPT the
 // racy global `dL_ddirect_shs += ...` (render_equation.cu:443-445): here each block reduces its
 // Gaussians' contributions and a second kernel sums the block partials in a fixed order.
 #include "r3dg_common.h"
@@ -624,7 +625,8 @@ static hipError_t launch_fwd(const BrdfKArgs& a, hipStream_t st) {
     const bool s16 = in.S_incident == 16 && in.S_direct == 16 && in.S_visibility == 16;
     const int Ns = in.sample_num;
     // a lane per (Gaussian, sample) while a workgroup holds at least one whole Gaussian; beyond 256
-    // samples the thread-per-Gaussian kernel (no call site uses more than 24)
+    // samples the thread-per-Gaussian kernel (training uses 24; the reference's relighting script
+    // runs the complex forward with --sample_num 384, which lands there)
     if (Ns >= 1 && Ns <= 256) {
         const int GB = 256 / Ns;
         const dim3 grid((in.P + GB - 1) / GB), block(256);
@@ -659,7 +661,8 @@ extern "C" int r3dg_render_equation_forward(const r3dg_brdf_inputs* in, int is_t
                                             r3dg_stream_t stream) {
     int rc = check_brdf_inputs(in);
     if (rc) return rc;
-    R3DG_REQUIRE(!is_training || rand_float || in->P == 0, "render_equation_forward: training needs rand_float");
+    R3DG_REQUIRE(!is_training || rand_float || in->P == 0 || in->sample_num == 0,
+                 "render_equation_forward: training needs rand_float");
     if (in->P == 0) return R3DG_OK;
     BrdfKArgs a{};
     a.in = *in;
