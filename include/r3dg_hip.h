@@ -315,6 +315,46 @@ int r3dg_render_equation_backward(const r3dg_brdf_inputs* in, const float* incid
                                   const float* dL_ddiffuse_light, r3dg_alloc_fn scratch_alloc, void* scratch_ctx,
                                   const r3dg_brdf_grads* out, r3dg_stream_t stream);
 
+/* ---- relighting render equation (gaussian_renderer/neilf_composite.py, scene/envmap.py) ------
+ * The forward-only operator of the reference's relighting script: its Python render equation
+ * (neilf_composite.py:241-334 with is_training=False, np.pi rather than the CUDA kernels' 3.14159),
+ * with SH widths up to degree 4 (25 coefficients, utils/sh_utils.py:131-182), the global light from
+ * nothing, the environment SH or a lat-long environment map, and the incident visibility from the
+ * baked SH or from per-sample traced values. Added within ABI 2: nothing existing changes. */
+enum { R3DG_LIGHT_NONE = 0, R3DG_LIGHT_SH = 1, R3DG_LIGHT_MAP = 2 };
+typedef struct r3dg_relight_inputs {
+    size_t struct_size;             /* sizeof(r3dg_relight_inputs); checked */
+    r3dg_brdf_inputs brdf;          /* P, the three SH widths (each 0..25 here), sample_num >= 1, the tensors;
+                                       direct_shs is read in R3DG_LIGHT_SH only, visibility_shs only without
+                                       traced_visibility */
+    int light_mode;                 /* R3DG_LIGHT_NONE: no global light (neilf_composite.py:267);
+                                       _SH: max(sum + 0.5, 0) of direct_shs (:260-263);
+                                       _MAP: the environment lookup below, unclamped (:265) */
+    const float* envmap;            /* [env_h, env_w, 3] lat-long map (R3DG_LIGHT_MAP) */
+    int env_h, env_w;
+    const float* env_transform;     /* device [3,3] row-major light rotation (light.transform), or NULL */
+    const float* traced_visibility; /* [P, sample_num] (pc._visibility_tracing, :121 / :274), or NULL for the
+                                       baked clamp(sum + 0.5, 0, 1) of visibility_shs (:270-271) */
+} r3dg_relight_inputs;
+
+/* Replaces the chunk loop over rendering_equation_python and the torch.cat of nine tensors
+ * (neilf_composite.py:106-133). features is one row-major [P,21] array in the order of :129-133:
+ * 0:3 rgb (:323-325), 3:6 normal, 6:9 base_color, 9 roughness, 10 metallic, 11:14 mean incident
+ * light, 14:17 mean local light, 17:20 mean global light (after the visibility product, :278),
+ * 20 mean visibility (:327-332); it is the rasterizer's S = 21 `features` as it stands.
+ * R3DG_ERR_ARG before any device work: a wrong struct_size, a width above 25, R3DG_LIGHT_MAP without a
+ * map or with env_h or env_w < 1, sample_num < 1 with P > 0. P = 0 returns at once. */
+int r3dg_render_equation_relight(const r3dg_relight_inputs* in, float* features, r3dg_stream_t stream);
+
+/* EnvLight.direct_light (scene/envmap.py:31-48) for n directions dirs [n,3] -> light [n,3]: d' = T d
+ * when env_transform is given, v = (d'.x, d'.z, -d'.y), tu = atan2(v.x, -v.z) / 2 pi + 0.5,
+ * tv = acos(clamp(v.y, -1, 1)) / pi, then nvdiffrast's dr.texture(filter_mode='linear') with its
+ * default boundary_mode='wrap' in both axes. The composite renderer's per-pixel background
+ * (neilf_composite.py:215) and the lookup of R3DG_LIGHT_MAP above. A texel index is in range for
+ * every direction, NaN and Inf included. */
+int r3dg_envmap_direct_light(int n, const float* dirs, const float* envmap, int env_h, int env_w,
+                             const float* env_transform, float* light, r3dg_stream_t stream);
+
 /* ---- shader manager (shaderManager.cu, preprocessModel.cu, ShShader.cu, splatShader.cu) ---- */
 
 enum { R3DG_SHADER_SH = 0, R3DG_SHADER_SPLAT = 1, R3DG_SHADER_POST = 2 };

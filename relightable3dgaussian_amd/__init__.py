@@ -14,6 +14,9 @@ distCUDA2`, scene/gaussian_model.py:13) (INTEGRATION.md).
 
 `relightable3dgaussian_amd.loss` is the training image loss (`ssim` of utils/loss_utils.py and the
 fused L1 + SSIM term of calculate_loss).
+
+`relightable3dgaussian_amd.relight` is the relighting script's render equation and environment-map
+light (gaussian_renderer/neilf_composite.py, scene/envmap.py).
 """
 from __future__ import annotations
 

@@ -477,6 +477,121 @@ render_equation_forward_complex(const torch::Tensor& base_color, const torch::Te
     return {pbr, dirs, lights, local, global, vis, diffuse, local_diffuse, accum, rgb_d, rgb_s};
 }
 
+// a float32 tensor on `dev` (a GPU), made contiguous; nothing is moved between devices
+torch::Tensor relight_tensor(const torch::Tensor& t, const char* name, const torch::Device& dev) {
+    TORCH_CHECK(t.is_cuda() && t.device() == dev, "relight: ", name, " must be on ", dev, ", got ", t.device());
+    TORCH_CHECK(t.scalar_type() == torch::kFloat32, "relight: ", name, " must be float32");
+    return t.contiguous();
+}
+
+// r3dg_render_equation_relight: rendering_equation_python of the relighting script
+// (neilf_composite.py:241-334) and the feature concatenation (:129-133) -> features [P, 21].
+// light_mode 0 none / 1 SH (direct_shs [1, S, 3]) / 2 map (envmap [He, We, 3], env_transform [3, 3] or
+// None); traced_visibility [P, Ns] or [P, Ns, 1], or None for the baked visibility_shs [P, S, 1].
+torch::Tensor render_equation_relight(const torch::Tensor& base_color, const torch::Tensor& roughness,
+                                      const torch::Tensor& metallic, const torch::Tensor& normals,
+                                      const torch::Tensor& viewdirs, const torch::Tensor& incidents_shs,
+                                      const std::optional<torch::Tensor>& direct_shs,
+                                      const std::optional<torch::Tensor>& visibility_shs, int64_t sample_num,
+                                      int64_t light_mode, const std::optional<torch::Tensor>& envmap,
+                                      const std::optional<torch::Tensor>& env_transform,
+                                      const std::optional<torch::Tensor>& traced_visibility) {
+    TORCH_CHECK(base_color.is_cuda(), "relight: base_color must be a GPU tensor (this build has no CPU path)");
+    const torch::Device dev = base_color.device();
+    const c10::OptionalDeviceGuard guard(dev);
+    TORCH_CHECK(base_color.dim() == 2 && base_color.size(1) == 3, "relight: base_color must be [P, 3]");
+    const int64_t P = base_color.size(0);
+    TORCH_CHECK(P <= INT32_MAX && sample_num <= INT32_MAX, "relight: P and sample_num must fit an int");
+    auto per_gaussian = [&](const torch::Tensor& t, const char* name, int64_t w) {
+        TORCH_CHECK(t.numel() == P * w && t.dim() >= 1 && t.size(0) == P, "relight: ", name, " must be [P, ", w, "]");
+        return relight_tensor(t, name, dev);
+    };
+    auto sh_rows = [&](const torch::Tensor& t, const char* name, int64_t rows, int64_t ch) {
+        TORCH_CHECK(t.dim() == 3 && t.size(0) == rows && t.size(2) == ch, "relight: ", name, " must be [", rows,
+                    ", S, ", ch, "]");
+        return relight_tensor(t, name, dev);
+    };
+    auto base = per_gaussian(base_color, "base_color", 3), rough = per_gaussian(roughness, "roughness", 1);
+    auto metal = per_gaussian(metallic, "metallic", 1), nrm = per_gaussian(normals, "normals", 3);
+    auto view = per_gaussian(viewdirs, "viewdirs", 3);
+    auto inc = sh_rows(incidents_shs, "incidents_shs", P, 3);
+    r3dg_relight_inputs in{};
+    in.struct_size = sizeof(in);
+    in.brdf.P = (int)P;
+    in.brdf.sample_num = (int)sample_num;
+    in.brdf.S_incident = (int)inc.size(1);
+    in.brdf.base_color = base.data_ptr<float>(); in.brdf.roughness = rough.data_ptr<float>();
+    in.brdf.metallic = metal.data_ptr<float>(); in.brdf.normals = nrm.data_ptr<float>();
+    in.brdf.viewdirs = view.data_ptr<float>(); in.brdf.incidents_shs = inc.data_ptr<float>();
+    in.light_mode = (int)light_mode;
+    torch::Tensor env, vis, map, xf, traced;  // keep the contiguous copies alive over the launch
+    if (light_mode == R3DG_LIGHT_SH) {
+        TORCH_CHECK(direct_shs.has_value(), "relight: light_mode SH needs direct_shs");
+        env = sh_rows(*direct_shs, "direct_shs", 1, 3);
+        in.brdf.S_direct = (int)env.size(1);
+        in.brdf.direct_shs = env.data_ptr<float>();
+    } else if (light_mode == R3DG_LIGHT_MAP) {
+        TORCH_CHECK(envmap.has_value(), "relight: light_mode MAP needs envmap");
+        TORCH_CHECK(envmap->dim() == 3 && envmap->size(2) == 3 && envmap->size(0) >= 1 && envmap->size(1) >= 1 &&
+                        envmap->size(0) <= INT32_MAX && envmap->size(1) <= INT32_MAX,
+                    "relight: envmap must be [He, We, 3]");
+        map = relight_tensor(*envmap, "envmap", dev);
+        in.envmap = map.data_ptr<float>();
+        in.env_h = (int)map.size(0);
+        in.env_w = (int)map.size(1);
+        if (env_transform.has_value()) {
+            TORCH_CHECK(env_transform->dim() == 2 && env_transform->size(0) == 3 && env_transform->size(1) == 3,
+                        "relight: env_transform must be [3, 3]");
+            xf = relight_tensor(*env_transform, "env_transform", dev);
+            in.env_transform = xf.data_ptr<float>();
+        }
+    }
+    if (traced_visibility.has_value()) {
+        const auto& tv = *traced_visibility;
+        TORCH_CHECK((tv.dim() == 2 || (tv.dim() == 3 && tv.size(2) == 1)) && tv.size(0) == P && tv.size(1) == sample_num,
+                    "relight: traced_visibility must be [P, sample_num] or [P, sample_num, 1]");
+        traced = relight_tensor(tv, "traced_visibility", dev);
+        // P = 0: an empty tensor's pointer may be null, which would read as "baked"
+        in.traced_visibility = P > 0 ? traced.data_ptr<float>() : nullptr;
+    } else {
+        TORCH_CHECK(visibility_shs.has_value(), "relight: needs visibility_shs or traced_visibility");
+        vis = sh_rows(*visibility_shs, "visibility_shs", P, 1);
+        in.brdf.S_visibility = (int)vis.size(1);
+        in.brdf.visibility_shs = vis.data_ptr<float>();
+    }
+    torch::Tensor features = torch::empty({P, 21}, base.options());
+    check(r3dg_render_equation_relight(&in, features.data_ptr<float>(), stream_of(dev)), "render_equation_relight");
+    return features;
+}
+
+// r3dg_envmap_direct_light: EnvLight.direct_light (scene/envmap.py:31-48), dirs [..., 3] -> [..., 3]
+torch::Tensor envmap_direct_light(const torch::Tensor& dirs, const torch::Tensor& envmap,
+                                  const std::optional<torch::Tensor>& env_transform) {
+    TORCH_CHECK(dirs.is_cuda(), "envmap_direct_light: dirs must be a GPU tensor (this build has no CPU path)");
+    const torch::Device dev = dirs.device();
+    const c10::OptionalDeviceGuard guard(dev);
+    TORCH_CHECK(dirs.dim() >= 1 && dirs.size(-1) == 3, "envmap_direct_light: dirs must be [..., 3]");
+    TORCH_CHECK(envmap.dim() == 3 && envmap.size(2) == 3 && envmap.size(0) >= 1 && envmap.size(1) >= 1 &&
+                    envmap.size(0) <= INT32_MAX && envmap.size(1) <= INT32_MAX,
+                "envmap_direct_light: envmap must be [He, We, 3]");
+    auto d = relight_tensor(dirs, "dirs", dev), map = relight_tensor(envmap, "envmap", dev);
+    const int64_t n = d.numel() / 3;
+    TORCH_CHECK(n <= INT32_MAX, "envmap_direct_light: too many directions");
+    torch::Tensor xf;
+    const float* xp = nullptr;
+    if (env_transform.has_value()) {
+        TORCH_CHECK(env_transform->dim() == 2 && env_transform->size(0) == 3 && env_transform->size(1) == 3,
+                    "envmap_direct_light: env_transform must be [3, 3]");
+        xf = relight_tensor(*env_transform, "env_transform", dev);
+        xp = xf.data_ptr<float>();
+    }
+    torch::Tensor light = torch::empty_like(d);
+    check(r3dg_envmap_direct_light((int)n, n ? d.data_ptr<float>() : nullptr, map.data_ptr<float>(), (int)map.size(0),
+                                   (int)map.size(1), xp, n ? light.data_ptr<float>() : nullptr, stream_of(dev)),
+          "envmap_direct_light");
+    return light;
+}
+
 // RenderEquationBackwardCUDA (render_equation.cu:494-547)
 std::tuple<torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor, torch::Tensor,
            torch::Tensor>
@@ -1151,6 +1266,9 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("rasterize_gaussians_backward_chunked", &rasterize_gaussians_backward_chunked);
     m.def("rasterize_gaussians_backward_chunked_packed", &rasterize_gaussians_backward_chunked_packed);
     m.def("render_equation_forward_with_rand", &render_equation_forward_with_rand);
+    // the relighting script's render equation and environment light (neilf_composite.py, envmap.py)
+    m.def("render_equation_relight", &render_equation_relight);
+    m.def("envmap_direct_light", &envmap_direct_light);
     m.def("rasterizer_state", &rasterizer_state);
     m.def("sh_color_grads", &sh_color_grads);
     m.def("sh_grad_from_views", &sh_grad_from_views);

@@ -1,0 +1,77 @@
+"""The relighting render equation: what the reference's `relighting.py` runs for every frame
+(gaussian_renderer/neilf_composite.py) and its environment-map light (scene/envmap.py), as one HIP
+kernel each (csrc/relight.hip, semantics in include/r3dg_hip.h `r3dg_render_equation_relight`).
+
+`EnvLight(envmap, scale=1.0)` -- the reference's class over an [He, We, 3] float32 GPU tensor in place of an
+.hdr path (decoding .hdr needs cv2). `.transform` is the optional [3, 3] light rotation and
+`.direct_light(dirs, transform=None)` the lat-long bilinear lookup for directions of any leading shape.
+
+`render_equation_relight(base_color, roughness, metallic, normals, viewdirs, incidents, env_light,
+visibility, sample_num, bake, visibility_precompute=None)` -> (rgb, extra_results, features) replaces the
+chunk loop over `rendering_equation_python` and the `torch.cat` of nine tensors
+(neilf_composite.py:106-133): `features` [P, 21] goes to the rasterizer as it is; `rgb` and the four
+`extra_results` entries (the reference's keys) are views into it.
+  env_light   None (no global light), an object with `get_env_shs` [1, S, 3] (the reference's
+              DirectLightEnv), or an EnvLight
+  visibility  the baked visibility SH [P, S, 1], read when `bake` is true
+  bake=False  the per-sample traced visibility `visibility_precompute` [P, Ns] or [P, Ns, 1]
+              (pc._visibility_tracing); without it a ValueError, as the reference raises
+Each SH width is 0..25. Forward only: the relighting script runs under torch.no_grad(). No CPU path and
+no torch fallback: the extension rejects CPU tensors.
+"""
+from __future__ import annotations
+
+import torch
+
+from . import _C
+
+LIGHT_NONE, LIGHT_SH, LIGHT_MAP = 0, 1, 2  # R3DG_LIGHT_* (include/r3dg_hip.h)
+
+# column ranges of `features` (neilf_composite.py:129-133)
+FEATURE_COLUMNS = {"rgb": (0, 3), "normal": (3, 6), "base_color": (6, 9), "roughness": (9, 10), "metallic": (10, 11),
+                   "incident_lights": (11, 14), "local_incident_lights": (14, 17),
+                   "global_incident_lights": (17, 20), "incident_visibility": (20, 21)}
+
+
+class EnvLight(torch.nn.Module):
+    """scene/envmap.py EnvLight over a tensor: `envmap` [He, We, 3] float32 on the GPU, multiplied by `scale`
+    as the reference's loader does."""
+
+    def __init__(self, envmap: torch.Tensor, scale: float = 1.0):
+        super().__init__()
+        if envmap.dim() != 3 or envmap.shape[2] != 3:
+            raise ValueError("EnvLight: envmap must be [He, We, 3], got %s" % (tuple(envmap.shape),))
+        self.scale = scale
+        self.device = envmap.device
+        self.envmap = (envmap.detach().to(torch.float32) * scale).contiguous()
+        self.transform = None
+
+    def direct_light(self, dirs: torch.Tensor, transform: torch.Tensor | None = None) -> torch.Tensor:
+        """Light from the map along dirs [..., 3] -> [..., 3]; `transform`, else `self.transform`, rotates
+        the directions first (d' = T d)."""
+        if transform is None:
+            transform = self.transform
+        return _C.envmap_direct_light(dirs, self.envmap, transform)
+
+
+@torch.no_grad()
+def render_equation_relight(base_color, roughness, metallic, normals, viewdirs, incidents, env_light, visibility,
+                            sample_num, bake, visibility_precompute=None):
+    if not bake and visibility_precompute is None:
+        raise ValueError("visibility should be pre-computed.")
+    direct_shs = envmap = transform = None
+    if env_light is None:
+        mode = LIGHT_NONE
+    elif isinstance(env_light, EnvLight):
+        mode, envmap, transform = LIGHT_MAP, env_light.envmap, env_light.transform
+    elif hasattr(env_light, "get_env_shs"):
+        mode, direct_shs = LIGHT_SH, env_light.get_env_shs
+    else:
+        raise TypeError("render_equation_relight: env_light must be None, an EnvLight or an object with get_env_shs")
+    features = _C.render_equation_relight(base_color, roughness, metallic, normals, viewdirs, incidents, direct_shs,
+                                          visibility if bake else None, int(sample_num), mode, envmap, transform,
+                                          None if bake else visibility_precompute)
+    cols = {k: features[:, a:b] for k, (a, b) in FEATURE_COLUMNS.items()}
+    extra_results = {k: cols[k] for k in ["incident_lights", "local_incident_lights", "global_incident_lights",
+                                          "incident_visibility"]}
+    return cols["rgb"], extra_results, features
