@@ -507,6 +507,98 @@ int r3dg_bvh_trace_opacity(int num_rays, int num_gaussians, const int32_t* nodes
                            float* rendered_opacity, r3dg_alloc_fn scratch_alloc, void* scratch_ctx,
                            r3dg_stream_t stream);
 
+/* Rays that start at Gaussian centres, for r3dg_bvh_trace_opacity_centres: no origin array exists.
+ * Ray r belongs to Gaussian g = index[r / sample_num] (g = r / sample_num when index is NULL, and
+ * then num_rays == sample_num * num_gaussians); its origin is means3D[g]. Its direction is
+ *   dirs != NULL: dirs[r], used as given (not normalised); with flip != 0 it is negated when
+ *                 (d.x * n.x + d.y * n.y) + d.z * n.z < 0 for n = normals[g], the sum in float32 in
+ *                 that order without contraction (a dot product of 0 does not flip): the call
+ *                 sites' `rays_d[(rays_d * normal).sum(-1) < 0] *= -1`
+ *   dirs == NULL: sample r % sample_num of fibonacci_sphere_sampling(normals[g], sample_num,
+ *                 random_rotate=False) (utils/graphics_utils.py:9-37), r3dg_fibonacci_dirs' values
+ * An index entry outside [0, num_gaussians) is the caller's error; it is not checked on the host (the
+ * array is on the device). Nothing is read for such a ray and its outputs are NaN and -1. */
+typedef struct r3dg_centre_rays {
+    size_t struct_size;   /* sizeof(r3dg_centre_rays); checked */
+    int num_rays;         /* R, a multiple of sample_num */
+    int sample_num;       /* Ns >= 1 rays per index entry */
+    const float* dirs;    /* [R, 3] or NULL (Fibonacci) */
+    const int32_t* index; /* [R / Ns] or NULL */
+    int flip;             /* given directions only */
+} r3dg_centre_rays;
+
+/* r3dg_bvh_trace_opacity for r3dg_centre_rays: the same traversal and outputs (rendered_opacity f32
+ * [R], num_contributes int32 [R] or NULL when the caller has no use for it). Nothing proportional
+ * to R is allocated: scratch is the 128 B per Gaussian of the packed records, plus, when the rays are
+ * traced in Morton order (>= 256k rays), 16 B per index entry (R / Ns sort keys; slot s then traces
+ * sample s % Ns of entry perm[s / Ns]) and the radix sort's workspace. R3DG_ERR_ARG: a wrong
+ * struct_size, sample_num < 1, num_rays no multiple of sample_num, num_rays != sample_num *
+ * num_gaussians without index. */
+int r3dg_bvh_trace_opacity_centres(const r3dg_centre_rays* rays, int num_gaussians, const int32_t* nodes,
+                                   const float* aabbs, const float* means3D, const float* cov3D_inv,
+                                   const float* opacities, const float* normals, int32_t* num_contributes,
+                                   float* rendered_opacity, r3dg_alloc_fn scratch_alloc, void* scratch_ctx,
+                                   r3dg_stream_t stream);
+
+/* fibonacci_sphere_sampling(normals, sample_num, random_rotate=False) as dirs [P, sample_num, 3] in one
+ * launch: what sample_incident_rays(normals, False, sample_num) returns as directions. Each direction is
+ * evaluated in double and rounded once, so it is the Fibonacci sample to float32 accuracy for every normal.
+ * r3dg_render_equation_relight evaluates the same samples in float32 as the reference's tensor code does
+ * (its sample angle is one rounded float32 product), which differs from these by up to 3e-5 rad at sample
+ * 383, and by up to 1e-3 of the direction for a normal within 1e-3 of -z. */
+int r3dg_fibonacci_dirs(int P, int sample_num, const float* normals, float* dirs, r3dg_stream_t stream);
+
+/* ---- visibility baking (gaussian_renderer/neilf.py:323-348, scene/gaussian_model.py:428-462) ----
+ * The L1 loss between traced visibility and the baked visibility SH. Per ray r of Gaussian
+ * g = index[r] (g = r without index, then R == P): d = dirs[r], flipped as r3dg_centre_rays' flip when
+ * normals is given; raw = eval_sh(sqrt(K) - 1, sh[g], d) in the operation order of
+ * utils/sh_utils.py:71-128, sh[g] = {sh_dc[g], sh_rest[g][0..K-2]}; s = clamp(raw + 0.5, 0, 1);
+ * term = |traced[r] - s|. K is 1, 4, 9, 16 or 25. An index entry outside [0, P) is the caller's error
+ * (not checked on the host); the loss is then NaN and the row is left out of the gradient. */
+typedef struct r3dg_visibility_sh_inputs {
+    size_t struct_size;   /* sizeof(r3dg_visibility_sh_inputs); checked */
+    int P, K, R;          /* Gaussians, coefficients per Gaussian, rays; P >= 1, R >= 1 */
+    float* sh_dc;         /* [P, 1, 1] visibility_dc; written by r3dg_visibility_sh_fit_step only */
+    float* sh_rest;       /* [P, K - 1, 1] visibility_rest (unused when K == 1); as sh_dc */
+    const float* dirs;    /* [R, 3] */
+    const float* traced;  /* [R] traced visibility */
+    const float* normals; /* [P, 3], or NULL: no flip */
+    const int32_t* index; /* [R], or NULL */
+} r3dg_visibility_sh_inputs;
+
+/* *loss (device) = mean over the rays of term. Deterministic: per-workgroup partial sums, added in a
+ * fixed order in f64 by a finishing workgroup; scratch is 4 B per 256 rays. */
+int r3dg_visibility_sh_loss_forward(const r3dg_visibility_sh_inputs* in, float* loss, r3dg_alloc_fn scratch_alloc,
+                                    void* scratch_ctx, r3dg_stream_t stream);
+
+/* Dense gradients grad_dc [P, 1, 1], grad_rest [P, K - 1, 1] of upstream * loss, every element written:
+ * d/dsh_k = *upstream * sign(s - traced) * [0 <= raw + 0.5 <= 1] * basis_k(d) / R (sign(0) = 0, the clamp
+ * bounds inclusive as torch's clamp backward), basis_k the factor of sh_k in eval_sh. upstream is a
+ * device scalar. Rows that index does not name are zero; a row named more than once accumulates (float
+ * atomics: reproducible bit for bit when the entries are distinct). */
+int r3dg_visibility_sh_loss_backward(const r3dg_visibility_sh_inputs* in, const float* upstream, float* grad_dc,
+                                     float* grad_rest, r3dg_stream_t stream);
+
+/* The Adam state of the two SH tensors for r3dg_visibility_sh_fit_step, in their layouts. */
+typedef struct r3dg_visibility_fit {
+    size_t struct_size;   /* sizeof(r3dg_visibility_fit); checked */
+    float* exp_avg_dc;    /* [P, 1, 1] */
+    float* exp_avg_rest;  /* [P, K - 1, 1] */
+    float* exp_avg_sq_dc;
+    float* exp_avg_sq_rest;
+    int step;             /* Adam's 1-based step count */
+    float lr;
+    double beta1, beta2, eps;
+} r3dg_visibility_fit;
+
+/* One iteration of finetune_visibility after its trace (gaussian_model.py:449-462), R == P and no index:
+ * one launch computes the gradient above with upstream 1 and applies one torch.optim.Adam step (the
+ * arithmetic of r3dg_adam_step) to the K coefficients of every Gaussian in place, a Gaussian with a zero
+ * gradient included (its moments decay and it moves, as for zero entries of a present gradient); the same
+ * launch leaves the loss partials, and *loss (device) is the mean L1 before the step. */
+int r3dg_visibility_sh_fit_step(const r3dg_visibility_sh_inputs* in, const r3dg_visibility_fit* fit, float* loss,
+                                r3dg_alloc_fn scratch_alloc, void* scratch_ctx, r3dg_stream_t stream);
+
 /* trace_bvh (bvh/src/bvh.cu:28-85, trace.cu:8-196): per ray the Gaussians of every crossed
  * subtree of <= 4 leaves, sorted by (ray, t); num_contributes int32 [R] is their count per ray.
  * The three lists (int32 [L], f32 [L, 3], int32 [L]) come from alloc; *num_rendered = L (one

@@ -17,6 +17,10 @@ fused L1 + SSIM term of calculate_loss).
 
 `relightable3dgaussian_amd.relight` is the relighting script's render equation and environment-map
 light (gaussian_renderer/neilf_composite.py, scene/envmap.py).
+
+`relightable3dgaussian_amd.visibility` is visibility baking: the traced per-sample visibility that
+render equation reads (relighting.py `update_visibility`), the visibility-SH training term
+(neilf.py `lambda_visibility`) and `finetune_visibility` (scene/gaussian_model.py).
 """
 from __future__ import annotations
 

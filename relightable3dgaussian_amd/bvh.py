@@ -42,6 +42,23 @@ class RayTracer:
                                             normals)
         return {"visibility": opa.unsqueeze(-1), "contribute": contrib.unsqueeze(-1)}
 
+    @torch.no_grad()
+    def trace_from_centres(self, rays_d, means3D, symm_inv, opacity, normals, index=None, flip=True,
+                           sample_num=None):
+        """`trace_visibility` for rays that start at Gaussian centres, without the origin array: ray r starts at
+        means3D[index[r // Ns]] (means3D[r // Ns] without index). rays_d [..., 3] holds Ns = sample_num (1 when
+        None) directions per origin, used as given; with `flip` a direction pointing below its Gaussian's normal
+        is negated first (the call sites' `rays_d[(rays_d * normal).sum(-1) < 0] *= -1`, decided in float32).
+        rays_d=None with sample_num=Ns traces the Ns Fibonacci directions about each normal
+        (visibility.fibonacci_dirs), computed in the kernel. Outputs shaped like `trace_visibility`'s:
+        rays_d's shape with 1 for its last axis, [G, Ns, 1] for Fibonacci rays."""
+        if rays_d is None and sample_num is None:
+            raise ValueError("trace_from_centres: rays_d=None (Fibonacci directions) needs sample_num")
+        contrib, opa = _C.trace_bvh_opacity_centres(self.tree, self.aabb, rays_d, means3D, symm_inv, opacity, normals,
+                                                    index, bool(flip), 1 if sample_num is None else int(sample_num),
+                                                    True)
+        return {"visibility": opa.unsqueeze(-1), "contribute": contrib.unsqueeze(-1)}
+
 
 def install_bvh_alias() -> None:
     """Make `from bvh import RayTracer` and `from bvh_tracing import _C` resolve here."""

@@ -24,6 +24,7 @@
 #include <cstring>
 
 #include "r3dg_common.h"
+#include "sh_dirs.h"  // fib_dir, flip_to_normal (shared with relight.hip, visibility.hip)
 
 #include <rocprim/rocprim.hpp>
 
@@ -391,7 +392,64 @@ struct TraceOpacityArgs {
     float* vis;
     int max_visits;  // 2 * nodes: a bound no valid tree reaches (each node is visited at most once)
     const uint32_t* perm;  // rays in Morton order of their origins (NULL: input order)
+    // rays from Gaussian centres (kRaysCentre*): rays_o is means3D [P, 3]; ray r belongs to
+    // Gaussian index[r / Ns] (r / Ns without index); perm then orders the n_rays / Ns ray groups
+    const float* normals;  // [P, 3]
+    const int32_t* index;  // [n_rays / Ns] or NULL
+    int Ns;
+    int flip;  // kRaysCentreDirs: negate a direction that points below its Gaussian's normal
+    int P;
 };
+
+// Where a trace kernel's rays come from. kRaysArray: the [R, 3] origin and direction arrays of
+// trace_bvh_opacity. kRaysCentreDirs / kRaysCentreFib: from the Gaussians' centres, so no origin
+// array exists; the direction is the caller's dirs[r] (flipped to the normal's side on request) or
+// sample r % Ns of the Fibonacci hemisphere about the normal (sh_dirs.h), computed in the lane.
+enum { kRaysArray = 0, kRaysCentreDirs = 1, kRaysCentreFib = 2 };
+
+// the ray traced in slot `slot` of the Morton order: perm[slot], or for centre rays group
+// perm[slot / Ns], sample slot % Ns
+template <int SRC>
+__device__ __forceinline__ int slot_ray(const TraceOpacityArgs& a, int slot) {
+    if (!a.perm) return slot;
+    if constexpr (SRC == kRaysArray) {
+        return (int)a.perm[slot];
+    } else {
+        const int q = slot / a.Ns;
+        return (int)a.perm[q] * a.Ns + (slot - q * a.Ns);
+    }
+}
+
+// origin and direction of ray `ray`; false for a centre ray whose index entry lies outside [0, P)
+// (the caller's error: nothing is read for it, and the kernels write NaN / -1 for the ray)
+template <int SRC>
+__device__ __forceinline__ bool load_ray(const TraceOpacityArgs& a, int ray, float3& o, float3& d) {
+    if constexpr (SRC == kRaysArray) {
+        o = ld3(a.rays_o, ray);
+        d = ld3(a.rays_d, ray);
+        return true;
+    } else {
+        const int q = ray / a.Ns;
+        const int g = a.index ? a.index[q] : q;
+        if ((unsigned)g >= (unsigned)a.P) return false;
+        o = ld3(a.rays_o, g);
+        const float3 n = ld3(a.normals, g);
+        if constexpr (SRC == kRaysCentreDirs) {
+            d = ld3(a.rays_d, ray);
+            if (a.flip) d = flip_to_normal(d, n);
+        } else {
+            d = fib_dir(n, ray - q * a.Ns, a.Ns);
+        }
+        return true;
+    }
+}
+
+// results of ray `ray`; contrib may be NULL for centre rays (the precompute discards it)
+template <int SRC>
+__device__ __forceinline__ void store_ray(const TraceOpacityArgs& a, int ray, int count, float vis) {
+    if (SRC == kRaysArray || a.contrib) a.contrib[ray] = count;
+    a.vis[ray] = vis;
+}
 
 // Blocks are dealt round-robin over the 8 XCDs (MI355X_MICROARCH.md, workgroup dispatch): give each
 // XCD a contiguous range of the Morton-sorted rays, so the rays sharing an L2 share tree nodes.
@@ -402,15 +460,24 @@ __device__ __forceinline__ int xcd_block() {
     return first + b / 8;
 }
 
-// Morton code of each ray origin in the root box (the leaf-code formula of bvh_morton_kernel)
+// Morton code of each ray origin in the root box (the leaf-code formula of bvh_morton_kernel).
+// Centre rays: one key per ray group, the origin being the group's Gaussian centre (rays_o is
+// means3D [P, 3]; a group whose index entry is out of range sorts with Gaussian 0).
+template <int SRC>
 __global__ void __launch_bounds__(256) bvh_ray_morton_kernel(int R, const float* __restrict__ rays_o,
+                                                             const int32_t* __restrict__ gaussian, int P,
                                                              const float* __restrict__ aabbs,
                                                              uint32_t* __restrict__ code,
                                                              uint32_t* __restrict__ index) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i >= R) return;
     const Box w = load_box(aabbs, 0);
-    const float3 o = ld3(rays_o, i);
+    int src = i;
+    if constexpr (SRC != kRaysArray) {
+        src = gaussian ? gaussian[i] : i;
+        if ((unsigned)src >= (unsigned)P) src = 0;
+    }
+    const float3 o = ld3(rays_o, src);
     const float px = fminf(fmaxf((o.x - w.lx) / (w.ux - w.lx) * 1024.f, 0.f), 1023.f);
     const float py = fminf(fmaxf((o.y - w.ly) / (w.uy - w.ly) * 1024.f, 0.f), 1023.f);
     const float pz = fminf(fmaxf((o.z - w.lz) / (w.uz - w.lz) * 1024.f, 0.f), 1023.f);
@@ -447,6 +514,7 @@ constexpr float kLogSlack = 2e-7f;
 // fell below 0.9" is the same event whatever the order: the group keeps a running log-domain sum
 // in LDS and every lane stops once it crosses the cut. Only the rounding of the product differs
 // from the reference's single chain (G = 1 keeps the reference's order exactly).
+template <int SRC>
 __global__ void __launch_bounds__(256) bvh_trace_opacity_kernel(TraceOpacityArgs a) {
     __shared__ int lstack[kLdsStack][256];
     __shared__ float lsum[256];  // per group: sum of log(1 - alpha) so far (-inf: cut)
@@ -455,15 +523,14 @@ __global__ void __launch_bounds__(256) bvh_trace_opacity_kernel(TraceOpacityArgs
     const int j = tid & ((1 << gb) - 1);
     const int gid = tid >> gb;  // group slot in this block
     const int slot = (int)(((long long)xcd_block() * blockDim.x + tid) >> gb);
-    const bool live = slot < a.n_rays;
-    const int ray = live && a.perm ? (int)a.perm[slot] : slot;
+    bool live = slot < a.n_rays;
+    const int ray = live ? slot_ray<SRC>(a, slot) : slot;
     if (j == 0) lsum[gid] = 0.f;
     __syncthreads();
     float3 o = make_float3(0.f, 0.f, 0.f), d = make_float3(0.f, 0.f, 1.f);
-    if (live) {
-        o = ld3(a.rays_o, ray);
-        d = ld3(a.rays_d, ray);
-    }
+    bool bad = false;  // a centre ray with an out-of-range index entry
+    if (live) bad = !load_ray<SRC>(a, ray, o, d);
+    if (SRC != kRaysArray && bad) live = false;
     int ostack[kBvhStack - kLdsStack];
     int sp = 0;
     auto push = [&](int v) {
@@ -542,10 +609,8 @@ __global__ void __launch_bounds__(256) bvh_trace_opacity_kernel(TraceOpacityArgs
         __syncthreads();  // every lane's updates are visible
         occluded = lsum[gid] < kLogCut || (double)T < 0.9;
     }
-    if (live && j == 0) {
-        a.contrib[ray] = occluded ? 0 : count;
-        a.vis[ray] = occluded ? 0.f : T;
-    }
+    if (live && j == 0) store_ray<SRC>(a, ray, occluded ? 0 : count, occluded ? 0.f : T);
+    if (SRC != kRaysArray && bad && j == 0) store_ray<SRC>(a, ray, -1, NAN);
 }
 
 // Few-rays variant with dynamic balancing: the G lanes of a ray's group share one LDS stack
@@ -566,6 +631,7 @@ __device__ __forceinline__ int group_incl_scan(int v, int width) {
     return v;
 }
 
+template <int SRC>
 __global__ void __launch_bounds__(256) bvh_trace_opacity_shared_kernel(TraceOpacityArgs a) {
     __shared__ int sstack[256 * kShared];
     __shared__ float lsum[256];
@@ -577,16 +643,15 @@ __global__ void __launch_bounds__(256) bvh_trace_opacity_shared_kernel(TraceOpac
     const uint64_t gmask = G == 64 ? ~0ull : (((1ull << G) - 1) << (lane & ~(G - 1)));
     const uint64_t below = (1ull << lane) - 1;
     const int slot = (int)(((long long)xcd_block() * blockDim.x + tid) >> gb);
-    const bool live = slot < a.n_rays;
-    const int ray = live && a.perm ? (int)a.perm[slot] : slot;
+    bool live = slot < a.n_rays;
+    const int ray = live ? slot_ray<SRC>(a, slot) : slot;
     const int C = kShared * G;
     int* st = sstack + gid * C;
     if (j == 0) lsum[gid] = 0.f;
     float3 o = make_float3(0.f, 0.f, 0.f), d = make_float3(0.f, 0.f, 1.f);
-    if (live) {
-        o = ld3(a.rays_o, ray);
-        d = ld3(a.rays_d, ray);
-    }
+    bool bad = false;  // a centre ray with an out-of-range index entry
+    if (live) bad = !load_ray<SRC>(a, ray, o, d);
+    if (SRC != kRaysArray && bad) live = false;
     int pstack[kBvhStack];
     int psp = 0;
     int sp = live ? 1 : 0;  // uniform within the group
@@ -675,10 +740,8 @@ __global__ void __launch_bounds__(256) bvh_trace_opacity_shared_kernel(TraceOpac
     }
     occluded = occluded || lsum[gid] < kLogCut || (double)T < 0.9;
     occluded = __ballot(occluded) & gmask;
-    if (live && j == 0) {
-        a.contrib[ray] = occluded ? 0 : count;
-        a.vis[ray] = occluded ? 0.f : T;
-    }
+    if (live && j == 0) store_ray<SRC>(a, ray, occluded ? 0 : count, occluded ? 0.f : T);
+    if (SRC != kRaysArray && bad && j == 0) store_ray<SRC>(a, ray, -1, NAN);
 }
 
 struct TraceListArgs {
@@ -800,6 +863,19 @@ __global__ void __launch_bounds__(256) bvh_trace_gather_kernel(int L, const uint
     pos_out[3 * (size_t)i + 2] = pos_in[3 * (size_t)s + 2];
 }
 
+// fibonacci_sphere_sampling(normals, Ns, random_rotate=False) as an array [P, Ns, 3]: what the
+// kRaysCentreFib trace computes per lane, for callers that want the directions themselves
+__global__ void __launch_bounds__(256) bvh_fib_dirs_kernel(int R, int Ns, const float* __restrict__ normals,
+                                                           float* __restrict__ dirs) {
+    const int r = blockIdx.x * blockDim.x + threadIdx.x;
+    if (r >= R) return;
+    const int g = r / Ns;
+    const float3 d = fib_dir(ld3(normals, g), r - g * Ns, Ns);
+    dirs[3 * (size_t)r] = d.x;
+    dirs[3 * (size_t)r + 1] = d.y;
+    dirs[3 * (size_t)r + 2] = d.z;
+}
+
 inline unsigned blocks(long long n) { return (unsigned)((n + 255) / 256); }
 inline size_t align256(size_t n) { return (n + 255) & ~(size_t)255; }
 
@@ -873,20 +949,14 @@ extern "C" int r3dg_bvh_build(int P, int32_t* nodes, float* aabbs, uint64_t* mor
     return R3DG_OK;
 }
 
-extern "C" int r3dg_bvh_trace_opacity(int num_rays, int num_gaussians, const int32_t* nodes, const float* aabbs,
-                                      const float* rays_o, const float* rays_d, const float* means3D,
-                                      const float* cov3D_inv, const float* opacities, const float* normals,
-                                      int32_t* num_contributes, float* rendered_opacity, r3dg_alloc_fn scratch_alloc,
-                                      void* scratch_ctx, r3dg_stream_t stream) {
-    R3DG_REQUIRE(num_rays >= 0, "trace_bvh_opacity: negative ray count");
-    if (num_rays == 0) return R3DG_OK;
-    R3DG_REQUIRE(num_gaussians >= 1, "trace_bvh_opacity: empty tree");
-    R3DG_REQUIRE(nodes && aabbs && rays_o && rays_d && means3D && cov3D_inv && opacities && normals &&
-                     num_contributes && rendered_opacity && scratch_alloc,
-                 "trace_bvh_opacity: null buffer");
-    R3DG_REQUIRE(((uintptr_t)aabbs & 7) == 0, "trace_bvh_opacity: aabbs must be 8-B aligned");
-    hipStream_t st = (hipStream_t)stream;
-    const int P = num_gaussians;
+// The opacity trace behind r3dg_bvh_trace_opacity (SRC = kRaysArray) and r3dg_bvh_trace_opacity_centres.
+// `a` arrives with the ray source and the outputs filled in (n_rays, rays_o, rays_d, contrib, vis, and
+// for centre rays normals, index, Ns, flip); the records, lanes per ray and ray order are set here.
+template <int SRC>
+static int trace_opacity_impl(TraceOpacityArgs a, int P, const int32_t* nodes, const float* aabbs,
+                              const float* means3D, const float* cov3D_inv, const float* opacities,
+                              const float* normals, r3dg_alloc_fn scratch_alloc, void* scratch_ctx, hipStream_t st) {
+    const int num_rays = a.n_rays;
     const size_t b_n = align256(64 * (size_t)std::max(P - 1, 1)), b_g = align256(64 * (size_t)P);
     char* s = (char*)scratch_alloc(scratch_ctx, b_n + b_g + 256);
     R3DG_REQUIRE(s, "trace_bvh_opacity: scratch allocation failed");
@@ -908,35 +978,113 @@ extern "C" int r3dg_bvh_trace_opacity(int num_rays, int num_gaussians, const int
         g_bits = 0;
         while (g_bits < 6 && (2 << g_bits) <= opt.test_bvh_lanes) ++g_bits;
     }
-    TraceOpacityArgs a{num_rays, P == 1 ? 1 : 0, g_bits, nrec, grec, rays_o, rays_d, num_contributes,
-                       rendered_opacity, 2 * (2 * P - 1), nullptr};
+    a.root_leaf = P == 1 ? 1 : 0;
+    a.g_bits = g_bits;
+    a.nrec = nrec;
+    a.grec = grec;
+    a.max_visits = 2 * (2 * P - 1);
+    a.perm = nullptr;
+    a.P = P;
     // rays in Morton order of their origins, each XCD taking a contiguous range (independent rays:
     // the results do not depend on it). Measured 1-3 % at 1M rays (8.84 -> 8.73 ms volume, 30.8 ->
     // 29.9 ms surface), a loss at 10k (the sort costs more than the locality gains), so only for
-    // >= 256k rays; test_bvh_sort = 1 / 2 forces it off / on
+    // >= 256k rays; test_bvh_sort = 1 / 2 forces it off / on. Centre rays share their group's origin:
+    // the n_rays / Ns groups are sorted, and slot s traces sample s % Ns of group perm[s / Ns], so
+    // the sort's arrays are per Gaussian, not per ray.
     const bool sort_rays = opt.test_bvh_sort ? opt.test_bvh_sort == 2 : num_rays >= 262144;
     if (P > 1 && sort_rays) {
+        const int n_keys = SRC == kRaysArray ? num_rays : num_rays / a.Ns;
         size_t sb = 0;
         R3DG_CHECK_HIP(rocprim::radix_sort_pairs(nullptr, sb, (uint32_t*)nullptr, (uint32_t*)nullptr,
-                                                 (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)num_rays, 0, 30, st));
-        const size_t b4 = align256(4 * (size_t)num_rays);
+                                                 (uint32_t*)nullptr, (uint32_t*)nullptr, (size_t)n_keys, 0, 30, st));
+        const size_t b4 = align256(4 * (size_t)n_keys);
         char* r = (char*)scratch_alloc(scratch_ctx, 4 * b4 + align256(sb) + 256);
         R3DG_REQUIRE(r, "trace_bvh_opacity: scratch allocation failed");
         r = (char*)(((uintptr_t)r + 255) & ~(uintptr_t)255);
         uint32_t *code = (uint32_t*)r, *idx = (uint32_t*)(r + b4), *code_s = (uint32_t*)(r + 2 * b4),
                  *perm = (uint32_t*)(r + 3 * b4);
-        hipLaunchKernelGGL(bvh_ray_morton_kernel, dim3(blocks(num_rays)), dim3(256), 0, st, num_rays, rays_o, aabbs,
-                           code, idx);
+        hipLaunchKernelGGL(bvh_ray_morton_kernel<SRC>, dim3(blocks(n_keys)), dim3(256), 0, st, n_keys, a.rays_o,
+                           a.index, P, aabbs, code, idx);
         R3DG_CHECK_HIP(hipGetLastError());
-        R3DG_CHECK_HIP(rocprim::radix_sort_pairs(r + 4 * b4, sb, code, code_s, idx, perm, (size_t)num_rays, 0, 30, st));
+        R3DG_CHECK_HIP(rocprim::radix_sort_pairs(r + 4 * b4, sb, code, code_s, idx, perm, (size_t)n_keys, 0, 30, st));
         a.perm = perm;
     }
     // G > 1: shared-stack groups (test_bvh_split: the static subtree split, for comparison)
     if (g_bits > 0 && !opt.test_bvh_split)
-        hipLaunchKernelGGL(bvh_trace_opacity_shared_kernel, dim3(blocks((long long)num_rays << g_bits)), dim3(256), 0,
-                           st, a);
+        hipLaunchKernelGGL(bvh_trace_opacity_shared_kernel<SRC>, dim3(blocks((long long)num_rays << g_bits)),
+                           dim3(256), 0, st, a);
     else
-        hipLaunchKernelGGL(bvh_trace_opacity_kernel, dim3(blocks((long long)num_rays << g_bits)), dim3(256), 0, st, a);
+        hipLaunchKernelGGL(bvh_trace_opacity_kernel<SRC>, dim3(blocks((long long)num_rays << g_bits)), dim3(256), 0,
+                           st, a);
+    R3DG_CHECK_HIP(hipGetLastError());
+    return R3DG_OK;
+}
+
+extern "C" int r3dg_bvh_trace_opacity(int num_rays, int num_gaussians, const int32_t* nodes, const float* aabbs,
+                                      const float* rays_o, const float* rays_d, const float* means3D,
+                                      const float* cov3D_inv, const float* opacities, const float* normals,
+                                      int32_t* num_contributes, float* rendered_opacity, r3dg_alloc_fn scratch_alloc,
+                                      void* scratch_ctx, r3dg_stream_t stream) {
+    R3DG_REQUIRE(num_rays >= 0, "trace_bvh_opacity: negative ray count");
+    if (num_rays == 0) return R3DG_OK;
+    R3DG_REQUIRE(num_gaussians >= 1, "trace_bvh_opacity: empty tree");
+    R3DG_REQUIRE(nodes && aabbs && rays_o && rays_d && means3D && cov3D_inv && opacities && normals &&
+                     num_contributes && rendered_opacity && scratch_alloc,
+                 "trace_bvh_opacity: null buffer");
+    R3DG_REQUIRE(((uintptr_t)aabbs & 7) == 0, "trace_bvh_opacity: aabbs must be 8-B aligned");
+    TraceOpacityArgs a{};
+    a.n_rays = num_rays;
+    a.rays_o = rays_o;
+    a.rays_d = rays_d;
+    a.contrib = num_contributes;
+    a.vis = rendered_opacity;
+    a.Ns = 1;
+    return trace_opacity_impl<kRaysArray>(a, num_gaussians, nodes, aabbs, means3D, cov3D_inv, opacities, normals,
+                                          scratch_alloc, scratch_ctx, (hipStream_t)stream);
+}
+
+extern "C" int r3dg_bvh_trace_opacity_centres(const r3dg_centre_rays* rays, int num_gaussians, const int32_t* nodes,
+                                              const float* aabbs, const float* means3D, const float* cov3D_inv,
+                                              const float* opacities, const float* normals,
+                                              int32_t* num_contributes, float* rendered_opacity,
+                                              r3dg_alloc_fn scratch_alloc, void* scratch_ctx, r3dg_stream_t stream) {
+    R3DG_REQUIRE(rays && rays->struct_size == sizeof(r3dg_centre_rays),
+                 "trace_bvh_opacity_centres: r3dg_centre_rays.struct_size does not match this library");
+    R3DG_REQUIRE(rays->num_rays >= 0 && rays->sample_num >= 1,
+                 "trace_bvh_opacity_centres: num_rays >= 0 and sample_num >= 1 expected");
+    R3DG_REQUIRE(rays->num_rays % rays->sample_num == 0,
+                 "trace_bvh_opacity_centres: num_rays must be a multiple of sample_num");
+    R3DG_REQUIRE(num_gaussians >= 1, "trace_bvh_opacity_centres: empty tree");
+    R3DG_REQUIRE(rays->index || rays->num_rays / rays->sample_num == num_gaussians,
+                 "trace_bvh_opacity_centres: without index, num_rays must be sample_num rays for every Gaussian");
+    if (rays->num_rays == 0) return R3DG_OK;
+    R3DG_REQUIRE(nodes && aabbs && means3D && cov3D_inv && opacities && normals && rendered_opacity && scratch_alloc,
+                 "trace_bvh_opacity_centres: null buffer");
+    R3DG_REQUIRE(((uintptr_t)aabbs & 7) == 0, "trace_bvh_opacity_centres: aabbs must be 8-B aligned");
+    TraceOpacityArgs a{};
+    a.n_rays = rays->num_rays;
+    a.rays_o = means3D;
+    a.rays_d = rays->dirs;
+    a.contrib = num_contributes;
+    a.vis = rendered_opacity;
+    a.normals = normals;
+    a.index = rays->index;
+    a.Ns = rays->sample_num;
+    a.flip = rays->flip;
+    if (rays->dirs)
+        return trace_opacity_impl<kRaysCentreDirs>(a, num_gaussians, nodes, aabbs, means3D, cov3D_inv, opacities,
+                                                   normals, scratch_alloc, scratch_ctx, (hipStream_t)stream);
+    return trace_opacity_impl<kRaysCentreFib>(a, num_gaussians, nodes, aabbs, means3D, cov3D_inv, opacities, normals,
+                                              scratch_alloc, scratch_ctx, (hipStream_t)stream);
+}
+
+extern "C" int r3dg_fibonacci_dirs(int P, int sample_num, const float* normals, float* dirs, r3dg_stream_t stream) {
+    R3DG_REQUIRE(P >= 0 && sample_num >= 1, "fibonacci_dirs: P >= 0 and sample_num >= 1 expected");
+    R3DG_REQUIRE((long long)P * sample_num < (1ll << 31), "fibonacci_dirs: P * sample_num must fit an int");
+    if (P == 0) return R3DG_OK;
+    R3DG_REQUIRE(normals && dirs, "fibonacci_dirs: null buffer");
+    hipLaunchKernelGGL(bvh_fib_dirs_kernel, dim3(blocks((long long)P * sample_num)), dim3(256), 0, (hipStream_t)stream,
+                       P * sample_num, sample_num, normals, dirs);
     R3DG_CHECK_HIP(hipGetLastError());
     return R3DG_OK;
 }

@@ -23,6 +23,7 @@
 // on its neighbours in the workgroup. No atomics. The [ng, 21] rows of a workgroup are one span.
 #include "r3dg_common.h"
 #include "r3dg_kernels.h"
+#include "sh_dirs.h"  // relight_fib_dir, the degree-4 SH constants (shared with bvh.hip, visibility.hip)
 
 namespace r3dg {
 
@@ -31,17 +32,6 @@ constexpr float kTwoPiF = 2.0f * kPiF;               // exact: the reference's 2
 constexpr int kRelightMaxSH = 25;                    // degree 4
 constexpr int kRelightCh = 16;                       // per-sample contributions summed per Gaussian
 constexpr int kRelightCols = 21;                     // feature row
-
-// degree-4 constants (utils/sh_utils.py:23-33); degrees 0..3 are r3dg_common.h's
-__device__ constexpr float SH_C4_0 = 2.5033429417967046f;
-__device__ constexpr float SH_C4_1 = -1.7701307697799304f;
-__device__ constexpr float SH_C4_2 = 0.9461746957575601f;
-__device__ constexpr float SH_C4_3 = -0.6690465435572892f;
-__device__ constexpr float SH_C4_4 = 0.10578554691520431f;
-__device__ constexpr float SH_C4_5 = -0.6690465435572892f;
-__device__ constexpr float SH_C4_6 = 0.47308734787878004f;
-__device__ constexpr float SH_C4_7 = -1.7701307697799304f;
-__device__ constexpr float SH_C4_8 = 0.6258357354491761f;
 
 // eval_sh_coef(4, d) (utils/sh_utils.py:131-182), the expressions as written there
 __device__ __forceinline__ void sh_coef25(float x, float y, float z, float* coef) {
@@ -59,33 +49,6 @@ __device__ __forceinline__ void sh_coef25(float x, float y, float z, float* coef
     coef[20] = SH_C4_4 * (zz * (35.0f * zz - 30.0f) + 3.0f); coef[21] = SH_C4_5 * xz * (7.0f * zz - 3.0f);
     coef[22] = SH_C4_6 * (xx - yy) * (7.0f * zz - 1.0f); coef[23] = SH_C4_7 * xz * (xx - 3.0f * yy);
     coef[24] = SH_C4_8 * (xx * (xx - 3.0f * yy) - yy * (3.0f * xx - yy));
-}
-
-// fibonacci_sphere_sampling(normals, Ns, random_rotate=False) (utils/graphics_utils.py:9-37) for one
-// sample. theta = float(delta) * ray is one rounded product, as the reference's tensor-by-scalar
-// product, so the sample angle carries the reference's own rounding (6e-5 rad at ray 383).
-__device__ __forceinline__ float3 relight_fib_dir(float3 n, int ray, int Ns) {
-    const float delta = (float)(3.14159265358979323846 * (3.0 - 2.23606797749978969641));
-    const float idx = (float)ray;
-    const float z = 1.0f - 2.0f * idx / (float)(2 * Ns - 1);
-    const float rad = sqrtf(1.0f - z * z);
-    const float theta = delta * idx;
-    float sn, cs;
-    sincosf(theta, &sn, &cs);
-    const float x = sn * rad, y = cs * rad;
-    float ox, oy, oz;
-    if (n.z + 1.0f > 0.0f) {  // rotation_between_z (utils/sh_utils.py:36-65), v3 = 0
-        const float v1 = -n.y, v2 = n.x;
-        const float cp1 = fmaxf(n.z + 1.0f, 1e-7f);
-        const float q12 = v1 * v2 / cp1;
-        ox = (1.0f + (-(v2 * v2)) / cp1) * x + q12 * y + v2 * z;
-        oy = q12 * x + (1.0f + (-(v1 * v1)) / cp1) * y + (-v1) * z;
-        oz = (-v2) * x + v1 * y + (1.0f + (-(v2 * v2) - v1 * v1) / cp1) * z;
-    } else {  // -I (:66-67)
-        ox = -x; oy = -y; oz = -z;
-    }
-    const float rn = fmaxf(sqrtf(ox * ox + oy * oy + oz * oz), 1e-12f);  // F.normalize
-    return make_float3(ox / rn, oy / rn, oz / rn);
 }
 
 // EnvLight.direct_light for one direction (scene/envmap.py:31-48): optional rotation, to_opengl,

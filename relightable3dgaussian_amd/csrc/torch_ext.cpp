@@ -1162,6 +1162,206 @@ std::tuple<torch::Tensor, torch::Tensor> trace_bvh_opacity(const torch::Tensor& 
     return {contrib, vis};
 }
 
+// ---- visibility baking (relightable3dgaussian_amd/visibility.py) -----------------------------------
+
+// index [G] of any integer type on the rays' device -> contiguous int32
+torch::Tensor index_i32(const torch::Tensor& index, const torch::Device& dev, const char* what) {
+    TORCH_CHECK(index.is_cuda() && index.device() == dev, what, ": index must be on ", dev);
+    TORCH_CHECK(index.dim() == 1 && (index.scalar_type() == torch::kInt32 || index.scalar_type() == torch::kInt64),
+                what, ": index must be a 1-D int32 or int64 tensor");
+    return index.to(torch::kInt32).contiguous();
+}
+
+// r3dg_bvh_trace_opacity_centres: rays from the centres of the Gaussians index names (all, without index).
+// rays_d [G, Ns, 3] / [G * Ns, 3] given directions, or None for sample_num Fibonacci directions per entry.
+// -> (contribute or None, visibility), shaped like rays_d without its last axis, [G, Ns] for Fibonacci rays
+std::tuple<std::optional<torch::Tensor>, torch::Tensor> trace_bvh_opacity_centres(
+    const torch::Tensor& nodes, const torch::Tensor& aabbs, const std::optional<torch::Tensor>& rays_d,
+    const torch::Tensor& means3D, const torch::Tensor& covs3D, const torch::Tensor& opacities,
+    const torch::Tensor& normals, const std::optional<torch::Tensor>& index, bool flip, int64_t sample_num,
+    bool want_contribute) {
+    const char* who = "trace_bvh_opacity_centres";
+    TORCH_CHECK(nodes.is_cuda() && nodes.scalar_type() == torch::kInt32, who, ": nodes int32 on GPU");
+    const auto nd = nodes.contiguous(), bx = cuda_f32(aabbs, "aabbs"), m = cuda_f32(means3D, "means3D"),
+               c = cuda_f32(covs3D, "covs3D"), op = cuda_f32(opacities, "opacities"), n = cuda_f32(normals, "normals");
+    const auto dev = m.device();
+    const int64_t P = m.numel() / 3;
+    TORCH_CHECK(P >= 1 && m.numel() == 3 * P && nd.numel() == 5 * (2 * P - 1) && bx.numel() == 6 * (2 * P - 1) &&
+                    c.numel() == 6 * P && op.numel() == P && n.numel() == 3 * P,
+                who, ": tree / Gaussian shapes disagree");
+    for (const auto* t : {&nd, &bx, &c, &op, &n})
+        TORCH_CHECK(t->device() == dev, who, ": every tensor must be on ", dev);
+    TORCH_CHECK(sample_num >= 1, who, ": sample_num must be at least 1");
+    torch::Tensor idx, d;
+    int64_t G = P;
+    if (index.has_value()) {
+        idx = index_i32(*index, dev, who);
+        G = idx.numel();
+    }
+    std::vector<int64_t> shape{G, sample_num};
+    if (rays_d.has_value()) {
+        d = cuda_f32(*rays_d, "rays_d");
+        TORCH_CHECK(d.device() == dev && d.dim() >= 1 && d.size(-1) == 3, who, ": rays_d [..., 3] on ", dev);
+        TORCH_CHECK(d.numel() == 3 * G * sample_num, who, ": rays_d must hold sample_num (", sample_num,
+                    ") directions for each of the ", G, " ray origins");
+        shape = d.sizes().slice(0, d.dim() - 1).vec();
+    }
+    const int64_t R = G * sample_num;
+    TORCH_CHECK(R <= INT32_MAX, who, ": too many rays");
+    const c10::OptionalDeviceGuard guard(dev);
+    auto vis = torch::empty(shape, m.options());
+    std::optional<torch::Tensor> contrib;
+    if (want_contribute) contrib = torch::empty(shape, m.options().dtype(torch::kInt32));
+    r3dg_centre_rays rays{};
+    rays.struct_size = sizeof(rays);
+    rays.num_rays = (int)R;
+    rays.sample_num = (int)sample_num;
+    rays.dirs = d.defined() ? d.data_ptr<float>() : nullptr;
+    rays.index = idx.defined() ? idx.data_ptr<int32_t>() : nullptr;
+    rays.flip = flip ? 1 : 0;
+    TensorAlloc scratch{m.options().dtype(torch::kUInt8), {}};
+    check(r3dg_bvh_trace_opacity_centres(&rays, (int)P, nd.data_ptr<int32_t>(), bx.data_ptr<float>(),
+                                         m.data_ptr<float>(), c.data_ptr<float>(), op.data_ptr<float>(),
+                                         n.data_ptr<float>(), contrib ? contrib->data_ptr<int32_t>() : nullptr,
+                                         vis.data_ptr<float>(), tensor_alloc, &scratch, stream_of(dev)),
+          who);
+    return {contrib, vis};
+}
+
+// r3dg_fibonacci_dirs: normals [P, 3] -> [P, sample_num, 3]
+torch::Tensor fibonacci_dirs(const torch::Tensor& normals, int64_t sample_num) {
+    const auto n = cuda_f32(normals, "fibonacci_dirs");
+    TORCH_CHECK(n.dim() == 2 && n.size(1) == 3, "fibonacci_dirs: normals [P, 3] expected");
+    TORCH_CHECK(sample_num >= 1 && n.size(0) * sample_num <= INT32_MAX, "fibonacci_dirs: sample_num out of range");
+    const c10::OptionalDeviceGuard guard(n.device());
+    auto out = torch::empty({n.size(0), sample_num, 3}, n.options());
+    check(r3dg_fibonacci_dirs((int)n.size(0), (int)sample_num, n.data_ptr<float>(), out.data_ptr<float>(),
+                              stream_of(n.device())),
+          "fibonacci_dirs");
+    return out;
+}
+
+// the checked inputs of the visibility-SH loss; the tensors keep the made-contiguous copies alive
+struct VisInputs {
+    torch::Tensor dc, rest, dirs, traced, normals, index;
+    r3dg_visibility_sh_inputs in;
+};
+
+VisInputs vis_inputs(const torch::Tensor& dc, const torch::Tensor& rest, const torch::Tensor& rays_d,
+                     const torch::Tensor& traced, const std::optional<torch::Tensor>& normals,
+                     const std::optional<torch::Tensor>& index, const char* who, bool in_place) {
+    VisInputs v{};
+    TORCH_CHECK(dc.is_cuda(), who, ": visibility_dc must be a GPU tensor (this build has no CPU path)");
+    const auto dev = dc.device();
+    auto f32 = [&](const torch::Tensor& t, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.device() == dev, who, ": ", name, " must be on ", dev, ", got ", t.device());
+        TORCH_CHECK(t.scalar_type() == torch::kFloat32, who, ": ", name, " must be float32");
+        TORCH_CHECK(!in_place || t.is_contiguous(), who, ": ", name, " is updated in place and must be contiguous");
+        return t.contiguous();
+    };
+    v.dc = f32(dc, "visibility_dc");
+    v.rest = f32(rest, "visibility_rest");
+    const int64_t P = v.dc.numel();
+    TORCH_CHECK(P >= 1 && v.dc.dim() >= 1 && v.dc.size(0) == P, who, ": visibility_dc must be [P, 1, 1]");
+    TORCH_CHECK(v.rest.dim() >= 1 && v.rest.size(0) == P && v.rest.numel() % P == 0, who,
+                ": visibility_rest must be [P, K - 1, 1] with visibility_dc's P");
+    const int64_t K = 1 + v.rest.numel() / P;
+    in_place = false;
+    v.dirs = f32(rays_d, "rays_d");
+    v.traced = f32(traced, "traced");
+    TORCH_CHECK(v.dirs.dim() >= 1 && v.dirs.size(-1) == 3, who, ": rays_d must be [R, 3]");
+    const int64_t R = v.dirs.numel() / 3;
+    TORCH_CHECK(v.traced.numel() == R, who, ": traced must hold one value per ray (", R, ")");
+    if (normals.has_value()) {
+        v.normals = f32(*normals, "normals");
+        TORCH_CHECK(v.normals.numel() == 3 * P, who, ": normals must be [P, 3]");
+    }
+    if (index.has_value()) {
+        v.index = index_i32(*index, dev, who);
+        TORCH_CHECK(v.index.numel() == R, who, ": index must name one Gaussian per ray (", R, ")");
+    } else {
+        TORCH_CHECK(R == P, who, ": without index, rays_d must hold one ray per Gaussian (P = ", P, ", R = ", R, ")");
+    }
+    TORCH_CHECK(P <= INT32_MAX && R <= INT32_MAX && K <= INT32_MAX, who, ": sizes must fit an int");
+    v.in = r3dg_visibility_sh_inputs{};
+    v.in.struct_size = sizeof(v.in);
+    v.in.P = (int)P; v.in.K = (int)K; v.in.R = (int)R;
+    v.in.sh_dc = v.dc.data_ptr<float>();
+    v.in.sh_rest = K > 1 ? v.rest.data_ptr<float>() : nullptr;
+    v.in.dirs = R ? v.dirs.data_ptr<float>() : nullptr;
+    v.in.traced = R ? v.traced.data_ptr<float>() : nullptr;
+    v.in.normals = v.normals.defined() ? v.normals.data_ptr<float>() : nullptr;
+    v.in.index = v.index.defined() && R ? v.index.data_ptr<int32_t>() : nullptr;
+    return v;
+}
+
+// mean over the rays of |traced - clamp(eval_sh(sh[g], d) + 0.5, 0, 1)| -> 0-dim tensor
+torch::Tensor visibility_sh_loss_forward(const torch::Tensor& dc, const torch::Tensor& rest,
+                                         const torch::Tensor& rays_d, const torch::Tensor& traced,
+                                         const std::optional<torch::Tensor>& normals,
+                                         const std::optional<torch::Tensor>& index) {
+    const auto v = vis_inputs(dc, rest, rays_d, traced, normals, index, "visibility_sh_loss_forward", false);
+    const c10::OptionalDeviceGuard guard(v.dc.device());
+    auto loss = torch::empty({}, v.dc.options());
+    TensorAlloc scratch{v.dc.options().dtype(torch::kUInt8), {}};
+    check(r3dg_visibility_sh_loss_forward(&v.in, loss.data_ptr<float>(), tensor_alloc, &scratch,
+                                          stream_of(v.dc.device())),
+          "visibility_sh_loss_forward");
+    return loss;
+}
+
+// -> (grad visibility_dc, grad visibility_rest), dense; upstream is a device scalar (no host read)
+std::tuple<torch::Tensor, torch::Tensor> visibility_sh_loss_backward(
+    const torch::Tensor& dc, const torch::Tensor& rest, const torch::Tensor& rays_d, const torch::Tensor& traced,
+    const std::optional<torch::Tensor>& normals, const std::optional<torch::Tensor>& index,
+    const torch::Tensor& upstream) {
+    const auto v = vis_inputs(dc, rest, rays_d, traced, normals, index, "visibility_sh_loss_backward", false);
+    TORCH_CHECK(upstream.is_cuda() && upstream.device() == v.dc.device() && upstream.numel() == 1 &&
+                    upstream.scalar_type() == torch::kFloat32,
+                "visibility_sh_loss_backward: upstream must be one float32 on the inputs' device");
+    const c10::OptionalDeviceGuard guard(v.dc.device());
+    auto gdc = torch::empty_like(v.dc), grest = torch::empty_like(v.rest);
+    check(r3dg_visibility_sh_loss_backward(&v.in, upstream.data_ptr<float>(), gdc.data_ptr<float>(),
+                                           v.in.K > 1 ? grest.data_ptr<float>() : nullptr, stream_of(v.dc.device())),
+          "visibility_sh_loss_backward");
+    return {gdc, grest};
+}
+
+// one fused fit step (gradient + Adam, in place) over one ray per Gaussian; the mean L1 before the step goes
+// to losses[slot]
+void visibility_sh_fit_step(torch::Tensor dc, torch::Tensor rest, const torch::Tensor& rays_d,
+                            const torch::Tensor& traced, const std::optional<torch::Tensor>& normals,
+                            torch::Tensor exp_avg_dc, torch::Tensor exp_avg_rest, torch::Tensor exp_avg_sq_dc,
+                            torch::Tensor exp_avg_sq_rest, int64_t step, double lr, double beta1, double beta2,
+                            double eps, torch::Tensor losses, int64_t slot) {
+    const char* who = "visibility_sh_fit_step";
+    const auto v = vis_inputs(dc, rest, rays_d, traced, normals, std::nullopt, who, true);
+    auto state = [&](const torch::Tensor& t, const torch::Tensor& like, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.device() == like.device() && t.scalar_type() == torch::kFloat32 &&
+                        t.is_contiguous() && t.numel() == like.numel(),
+                    who, ": ", name, " must be a contiguous float32 tensor of its parameter's size and device");
+        return t.data_ptr<float>();
+    };
+    TORCH_CHECK(losses.is_cuda() && losses.device() == v.dc.device() && losses.scalar_type() == torch::kFloat32 &&
+                    losses.is_contiguous() && slot >= 0 && slot < losses.numel(),
+                who, ": losses must be a contiguous float32 tensor on the inputs' device holding slot ", slot);
+    TORCH_CHECK(step >= 1 && step <= INT32_MAX, who, ": step must be >= 1");
+    r3dg_visibility_fit fit{};
+    fit.struct_size = sizeof(fit);
+    fit.exp_avg_dc = state(exp_avg_dc, v.dc, "exp_avg_dc");
+    fit.exp_avg_sq_dc = state(exp_avg_sq_dc, v.dc, "exp_avg_sq_dc");
+    fit.exp_avg_rest = v.in.K > 1 ? state(exp_avg_rest, v.rest, "exp_avg_rest") : nullptr;
+    fit.exp_avg_sq_rest = v.in.K > 1 ? state(exp_avg_sq_rest, v.rest, "exp_avg_sq_rest") : nullptr;
+    fit.step = (int)step;
+    fit.lr = (float)lr;
+    fit.beta1 = beta1; fit.beta2 = beta2; fit.eps = eps;
+    const c10::OptionalDeviceGuard guard(v.dc.device());
+    TensorAlloc scratch{v.dc.options().dtype(torch::kUInt8), {}};
+    check(r3dg_visibility_sh_fit_step(&v.in, &fit, losses.data_ptr<float>() + slot, tensor_alloc, &scratch,
+                                      stream_of(v.dc.device())),
+          who);
+}
+
 struct MultiAllocBvh {
     torch::TensorOptions opts;
     std::vector<torch::Tensor> ts;
@@ -1289,6 +1489,16 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("trace_bvh", &trace_bvh);
     m.def("trace_bvh_opacity", &trace_bvh_opacity);
     m.def("bvh_leaf_aabbs", &bvh_leaf_aabbs);
+    // visibility baking (relightable3dgaussian_amd/visibility.py): rays from Gaussian centres, the
+    // visibility-SH loss and the fused fit step
+    m.def("trace_bvh_opacity_centres", &trace_bvh_opacity_centres, py::arg("nodes"), py::arg("aabbs"),
+          py::arg("rays_d"), py::arg("means3D"), py::arg("covs3D"), py::arg("opacities"), py::arg("normals"),
+          py::arg("index") = py::none(), py::arg("flip") = true, py::arg("sample_num") = 1,
+          py::arg("want_contribute") = true);
+    m.def("fibonacci_dirs", &fibonacci_dirs);
+    m.def("visibility_sh_loss_forward", &visibility_sh_loss_forward);
+    m.def("visibility_sh_loss_backward", &visibility_sh_loss_backward);
+    m.def("visibility_sh_fit_step", &visibility_sh_fit_step);
     // nearest-neighbour distances: the reference's simple_knn._C (submodules/simple-knn/ext.cpp)
     m.def("distCUDA2", &dist_cuda2);
     // the fused L1 + SSIM image loss (relightable3dgaussian_amd/loss.py)
