@@ -350,7 +350,7 @@ constexpr int kBwdGrp = 13;  // instances per MFMA group of the DMA-staged kerne
 // (instance, wave) instead of per pixel): no partial rows, no row flags, no row_sum_kernel; sums
 // depend on the atomics' arrival order. !ATOM: the deterministic partial rows + row_sum_kernel.
 // WS: bf16 terms of w in the X products (kBwdSplit, default 2); WS = 1 is the one-term
-// reduction the gradient parity bar must reject (R3DG_BWD_WTERMS=1, tests/test_gpu_parity.py
+// reduction the gradient parity bar must reject (r3dg_options.test_bwd_wterms = 1, tests/test_gpu_parity.py
 // test_one_term_reduction_fails_bar).
 template <int SMAX, bool ATOM, int WS = kBwdSplit>
 __global__ void __launch_bounds__(kBlock) __attribute__((amdgpu_waves_per_eu(SMAX <= 12 ? kBwdWaves : 1)))
@@ -437,10 +437,13 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
     const int nch = l & 15;
     const float4* st = stage;  // staging buffer of the current batch
 
-    auto step = [&](int j, int p, bool live, float opacity, float power, float G, float& wv, float& qv,
-                    bool& okv) {
+    // Staged instance j of the batch ending at tile position hi sits at position hi - 1 - j, which
+    // this pixel blended iff it lies below the pixel's n_contrib: j >= hi - last. jlim = hi - last per
+    // lane, stepped once per batch: no scalar subtraction per visit.
+    int jlim = max_last - last;
+    // ju: the staged instance (a scalar from the live-mask walk)
+    auto step = [&](int ju, float opacity, float power, float G, float& wv, float& qv) {
 #pragma clang fp contract(off)
-        const int ju = __builtin_amdgcn_readfirstlane(j);
         float v[NA4 * 4];
 #pragma unroll
         for (int q = 0; q < NA4; ++q) {
@@ -450,8 +453,7 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
         // (the last row stays a ds_read_b96 at S = 11: the forward's whole-float4 read measured
         // +0.4 % here, profiles/r06/b128_prio_ab)
         const float alpha = fminf(0.99f, opacity * G);
-        const bool ok = live && p < last && !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
-        okv = ok;
+        const bool ok = ju >= jlim && !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
         const float ae = ok ? alpha : 0.f;
         const float Ge = ok ? G : 0.f;
         const float rinv = __builtin_amdgcn_rcpf(1.f - ae);
@@ -646,7 +648,7 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
     auto batch_bits = [&](int hi_b) -> uint32_t {
         return l < min(NB, hi_b) ? (uint32_t)a.contrib[range.x + (uint32_t)(hi_b - 1 - l)] : 0u;
     };
-    int r = 0;
+    int r = 0;  // rows in the current MFMA group, times WQS (put_row)
     uint32_t gid_cur = max_last > 0 ? batch_gid(max_last) : 0u;  // Gaussian of instance l of the current batch
     if (max_last > 0) issue(gid_cur, 0);
     uint32_t gid_next = max_last > NB ? batch_gid(max_last - NB) : 0u;
@@ -684,12 +686,11 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
             a.flags[row_l] = 1;
         }
         if (l == 0) R3DG_EXP_ADD(0, __builtin_popcountll(bits));
-        auto rec0 = [&](int j) { return st[__builtin_amdgcn_readfirstlane(j)]; };
-        auto pos = [&](int j) {
-            return *reinterpret_cast<const float2*>(st + NB + __builtin_amdgcn_readfirstlane(j));
-        };
-        while (bits) {
-            int j0, j1;
+        auto pos = [&](int ju) { return *reinterpret_cast<const float2*>(st + NB + ju); };
+        // the next pair from the live mask by s_ff1 + s_bitset0 (s_ff1 of an empty mask is -1, whose
+        // s_bitset0 clears the already clear top bit); j1 < 0: fewer than two instances were left
+        int j0, j1;
+        auto next_pair = [&]() {
             if constexpr (NB > 32) {
                 unsigned long long b = bits;
                 asm("s_ff1_i32_b64 %0, %2\n\ts_bitset0_b64 %2, %0\n\ts_ff1_i32_b64 %1, %2\n\ts_bitset0_b64 %2, %1"
@@ -701,41 +702,60 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
                     : "=&s"(j0), "=&s"(j1), "+s"(b));
                 bits = b;
             }
-            const bool has1 = j1 >= 0;
-            j1 = has1 ? j1 : j0;
-            const float4 co0 = rec0(j0), co1 = rec0(j1);
+        };
+        // every visited instance was blended by a pixel of this wave: one group row each; the
+        // lane that holds the instance's row id (lane j of the batch) also writes it into the image
+        // row's pad column (the flush reads it): one compare per visit. Handing it to lane 0 with
+        // a v_readlane and a copy back to a VGPR measured 2.4 % slower
+        // (ro: the row's offset in the image, r * WQS, kept as the group's counter: no multiply per visit)
+        auto put_row = [&](int ro, int ju, float wv, float qv) {
+            float* wr = wq + ro + l;
+            wr[0] = wv;
+            wr[GRP * WQS] = qv;
+            if (l == ju) reinterpret_cast<uint32_t*>(wq)[GRP * WQS + ro + 64] = row_l;
+        };
+        // Pairs while the mask holds two instances (both valid: no select or predicate for a missing
+        // second one), then an odd count's last instance in a one-visit body after the loop
+        // (wave-uniform). A pair starts with at most GRP - 2 rows in the group, the tail with at most GRP - 1.
+        next_pair();
+        while (j1 >= 0) {
+            if (l == 0) R3DG_EXP_ADD(2, 1);
+            const float4 co0 = st[j0], co1 = st[j1];
             const float2 xy0 = pos(j0), xy1 = pos(j1);
             const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
             const float pw1 = gauss_power(co1, xy1.x - pfx, xy1.y - pfy);
             float G0 = fast_expf(pw0), G1 = fast_expf(pw1);
             settle_threshold2(pw0, co0.w, G0, pw1, co1.w, G1);
             float wv0, qv0, wv1, qv1;
-            bool ok0, ok1;
-            step(j0, hi - 1 - j0, true, co0.w, pw0, G0, wv0, qv0, ok0);
-            step(j1, hi - 1 - j1, has1, co1.w, pw1, G1, wv1, qv1, ok1);
-            (void)ok0;
-            (void)ok1;
-            // every visited instance was blended by a pixel of this wave: one group row each; the
-            // lane that holds the instance's row id (lane j of the batch) also writes it into the image
-            // row's pad column (the flush reads it): one compare per visit. Handing it to lane 0 with
-            // a v_readlane and a copy back to a VGPR measured 2.4 % slower
-            {
-                float* wr = wq + r * WQS + l;
-                wr[0] = wv0;
-                wr[GRP * WQS] = qv0;
-                if (l == j0) reinterpret_cast<uint32_t*>(wq)[(GRP + r) * WQS + 64] = row_l;
-            }
-            if (has1) {
-                float* wr = wq + (r + 1) * WQS + l;
-                wr[0] = wv1;
-                wr[GRP * WQS] = qv1;
-                if (l == j1) reinterpret_cast<uint32_t*>(wq)[(GRP + r + 1) * WQS + 64] = row_l;
-            }
-            r += has1 ? 2 : 1;
-            if (r > GRP - 2) {
-                flush(r);
+            step(j0, co0.w, pw0, G0, wv0, qv0);
+            step(j1, co1.w, pw1, G1, wv1, qv1);
+            put_row(r, j0, wv0, qv0);
+            put_row(r + WQS, j1, wv1, qv1);
+            r += 2 * WQS;
+            if (r > (GRP - 2) * WQS) {
+                flush(r / WQS);
                 r = 0;
             }
+            next_pair();
+        }
+        if (j0 >= 0) {
+            // the same statements as one half of the pair (settle_threshold is settle_threshold2's
+            // decision on one value): an instance's bits do not depend on which body visits it
+            if (l == 0) R3DG_EXP_ADD(2, 1);
+            const float4 co0 = st[j0];
+            const float2 xy0 = pos(j0);
+            const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
+            const float G0 = settle_threshold(pw0, co0.w, fast_expf(pw0));
+            float wv0, qv0;
+            step(j0, co0.w, pw0, G0, wv0, qv0);
+            put_row(r, j0, wv0, qv0);
+            r += WQS;
+        }
+        // the group's flush after a tail that filled it (the next pair needs two free rows) and the
+        // last group's after the last batch share one copy of the flush
+        if (r > (GRP - 2) * WQS || (hn <= 0 && r > 0)) {
+            flush(r / WQS);
+            r = 0;
         }
         // the next batch's records have landed (this wave's DMA) and every wave is done with
         // this buffer before the next iteration's DMA overwrites it
@@ -743,8 +763,8 @@ render_bwd_glds_kernel(RenderBwdArgs a) {
         __syncthreads();
         buf ^= 1;
         gid_cur = gid_staged;
+        jlim -= NB;
     }
-    if (r > 0) flush(r);
 }
 
 template <int SMAX>

@@ -212,10 +212,9 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
             }
             bits[h] = __ballot(mine);
         }
-        // j: the staged instance
-        auto step = [&](int j, bool live, float opacity, float power, float G) {
-#pragma clang fp contract(off)  // explicit FMAs only: both unrolled copies round alike
-            const int ju = __builtin_amdgcn_readfirstlane(j);
+        // ju: the staged instance (a scalar from the live-mask walk)
+        auto step = [&](int ju, float opacity, float power, float G) {
+#pragma clang fp contract(off)  // explicit FMAs only: the pair's two copies and the tail's one round alike
             float v[NA4 * 4];
 #pragma unroll
             for (int q = 0; q < NA4; ++q) {
@@ -224,7 +223,7 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
                 v[4 * q] = r.x; v[4 * q + 1] = r.y; v[4 * q + 2] = r.z; v[4 * q + 3] = r.w;
             }
             const float alpha = fminf(0.99f, opacity * G);  // bit-identical to the oracle
-            const bool contrib = live && !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
+            const bool contrib = !(power > 0.0f) && !(alpha < 1.0f / 255.0f);
             const float test_T = T * (1.0f - alpha);
             const bool stop = test_T < 0.0001f;  // also every step after the pixel's stop (T < 0)
             if (contrib && stop) T = -fabsf(T);
@@ -247,7 +246,7 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
                 Dp = __builtin_fmaf(v[3], wgt, Dp);
                 Op += wgt;
                 T = test_T;
-                last = (uint32_t)(base + j + 1);
+                last = (uint32_t)(base + ju + 1);
                 s_cf[(buf * 64 + ju) * 8 + 2 * w + (l >> 5)] = 1;  // every accumulating lane of a half: one byte
             }
         };
@@ -255,30 +254,47 @@ render_fwd_glds_kernel(RenderFwdArgs a) {
         unsigned long long b = bits[0];
         if (l == 0) R3DG_EXP_ADD(3, __builtin_popcountll(b));
         if (__ballot(!(T < 0.0f)) == 0ull) b = 0ull;  // (every pixel of the wave stopped)
-        while (b) {
-            // the pair from the live mask by s_ff1 + s_bitset0 (s_ff1 of an empty mask is -1, whose
-            // s_bitset0 clears the already clear bit 63): 4 scalar ops for what b &= b - 1 twice,
-            // two s_ff1 and their selects took 11
-            int j0, j1;
+        // the next pair from the live mask by s_ff1 + s_bitset0 (s_ff1 of an empty mask is -1, whose
+        // s_bitset0 clears the already clear bit 63): 4 scalar ops for what b &= b - 1 twice, two
+        // s_ff1 and their selects took 11. j1 < 0: fewer than two instances were left
+        int j0, j1;
+        auto next_pair = [&]() {
             asm("s_ff1_i32_b64 %0, %2\n\ts_bitset0_b64 %2, %0\n\ts_ff1_i32_b64 %1, %2\n\ts_bitset0_b64 %2, %1"
                 : "=&s"(j0), "=&s"(j1), "+s"(b));
-            const bool has1 = j1 >= 0;
-            j1 = has1 ? j1 : j0;
-            const int u0 = __builtin_amdgcn_readfirstlane(j0), u1 = __builtin_amdgcn_readfirstlane(j1);
-            const float4 co0 = st[u0], co1 = st[u1];
-            const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + u0);
-            const float2 xy1 = *reinterpret_cast<const float2*>(st + NB + u1);
+        };
+        next_pair();
+        // Pairs while the mask holds two instances, then an odd count's last instance in a one-visit
+        // body after the loop (wave-uniform): the pair body runs with both instances valid, without
+        // selects or predicates for a missing second one. The loop has one exit, at its top: with a
+        // second one (a break) the compiler keeps two copies of the accumulators and spills.
+        while (j1 >= 0) {
+            if (l == 0) R3DG_EXP_ADD(0, 1);
+            const float4 co0 = st[j0], co1 = st[j1];
+            const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + j0);
+            const float2 xy1 = *reinterpret_cast<const float2*>(st + NB + j1);
             const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
             const float pw1 = gauss_power(co1, xy1.x - pfx, xy1.y - pfy);
             // two scalar exp chains, interleaved by the scheduler (the packed pair, r3dg_expf2,
             // needs an s_nop between its dependent v_pk_fma_f32: 0.3 % slower at M1)
             const f32x2 G = {r3dg_expf(pw0), r3dg_expf(pw1)};
-            step(j0, true, co0.w, pw0, G.x);
-            step(j1, has1, co1.w, pw1, G.y);
-            if (l == 0) R3DG_EXP_ADD(2, has1 ? 2 : 1);
-            // converged here: a uniform exit (testing every 2 or 4 iterations instead, which
-            // drops ~10 scalar instructions per iteration, measured no faster in round 3)
-            if (__ballot(!(T < 0.0f)) == 0ull) break;
+            step(j0, co0.w, pw0, G.x);
+            step(j1, co1.w, pw1, G.y);
+            if (l == 0) R3DG_EXP_ADD(2, 2);
+            // converged here: a uniform exit, as an emptied mask (testing every 2 or 4 iterations
+            // instead, which drops ~10 scalar instructions per iteration, measured no faster in
+            // round 3)
+            if (__ballot(!(T < 0.0f)) == 0ull) b = 0ull;
+            next_pair();
+        }
+        if (j0 >= 0) {
+            // the same statements as one half of the pair: an instance's bits do not depend on which
+            // body blends it
+            if (l == 0) R3DG_EXP_ADD(0, 1);
+            const float4 co0 = st[j0];
+            const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + j0);
+            const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
+            step(j0, co0.w, pw0, r3dg_expf(pw0));
+            if (l == 0) R3DG_EXP_ADD(2, 1);
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         buf ^= 1;
@@ -421,12 +437,11 @@ __global__ void __launch_bounds__(kBlock) intermediate_glds_kernel(IntermediateA
         }
         unsigned long long bits = __ballot(mine);
         // the tests predicated, only the accumulation a branch (as the blend's step)
-        auto step = [&](int j, bool live, float power, float G) {
-            const int ju = __builtin_amdgcn_readfirstlane(j);
+        auto step = [&](int ju, float power, float G) {
             const float o = st[ju].w;
             const float4 ds = st[2 * NB + ju];  // depth, stencil, stencil opacity
             const float alpha = fminf(0.99f, o * G), salpha = fminf(0.99f, ds.z * G);
-            const bool contrib = live && !done && !(power > 0.0f) &&
+            const bool contrib = !done && !(power > 0.0f) &&
                                  !(alpha < 1.0f / 255.0f && salpha < 1.0f / 255.0f);
             const float tT = T * (1 - alpha), tS = sT * (1 - salpha);
             const bool stop = tT < 0.0001f && tS < 0.0001f;
@@ -438,21 +453,31 @@ __global__ void __launch_bounds__(kBlock) intermediate_glds_kernel(IntermediateA
                 sT = tS;
             }
         };
-        while (bits && __ballot(!done) != 0ull) {
-            const int j0 = (int)__builtin_ctzll(bits);
-            bits &= bits - 1;
-            const bool has1 = bits != 0ull;
-            const int j1 = has1 ? (int)__builtin_ctzll(bits) : j0;
-            bits &= bits - 1;
-            const int u0 = __builtin_amdgcn_readfirstlane(j0), u1 = __builtin_amdgcn_readfirstlane(j1);
-            const float4 co0 = st[u0], co1 = st[u1];
-            const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + u0);
-            const float2 xy1 = *reinterpret_cast<const float2*>(st + NB + u1);
+        // pairs while two live instances remain, then an odd count's last one in a one-visit body, as
+        // the default blend (a wave whose pixels are all done takes no further instance)
+        int j0, j1;
+        auto next_pair = [&]() {
+            if (__ballot(!done) == 0ull) bits = 0ull;
+            asm("s_ff1_i32_b64 %0, %2\n\ts_bitset0_b64 %2, %0\n\ts_ff1_i32_b64 %1, %2\n\ts_bitset0_b64 %2, %1"
+                : "=&s"(j0), "=&s"(j1), "+s"(bits));
+        };
+        next_pair();
+        while (j1 >= 0) {
+            const float4 co0 = st[j0], co1 = st[j1];
+            const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + j0);
+            const float2 xy1 = *reinterpret_cast<const float2*>(st + NB + j1);
             const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
             const float pw1 = gauss_power(co1, xy1.x - pfx, xy1.y - pfy);
             const f32x2 G = {r3dg_expf(pw0), r3dg_expf(pw1)};  // scalar chains, as the default blend
-            step(j0, true, pw0, G.x);
-            step(j1, has1, pw1, G.y);
+            step(j0, pw0, G.x);
+            step(j1, pw1, G.y);
+            next_pair();
+        }
+        if (j0 >= 0) {
+            const float4 co0 = st[j0];
+            const float2 xy0 = *reinterpret_cast<const float2*>(st + NB + j0);
+            const float pw0 = gauss_power(co0, xy0.x - pfx, xy0.y - pfy);
+            step(j0, pw0, r3dg_expf(pw0));
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         buf ^= 1;

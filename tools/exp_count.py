@@ -18,3 +18,7 @@ print(f"bwd live pairs: {buf[0]}\nbwd mfma groups: {buf[1]}")
 # bench.main runs the warm-up steps, the timed steps and as many profiled steps: 2 at --steps 1
 print("m1 steps run: 2")
 print(f"fwd steps done: {fb[2]}\nfwd live pairs (pre-exit): {fb[3]}")
+# walk iterations (a pair or an odd count's one-visit tail each): 2 x iterations - steps = the tails, which
+# were predicated-off second steps ("phantoms") before the tail had a body of its own
+print(f"bwd walk iterations: {buf[2]}\nbwd one-visit tails: {2 * buf[2] - buf[0]}")
+print(f"fwd walk iterations: {fb[0]}\nfwd one-visit tails: {2 * fb[0] - fb[2]}")

@@ -10,7 +10,9 @@ branch) and, for VALU, by role using the operand patterns of render_fwd.hip / re
           polynomial constants, v_lshl_add exponent add) or v_exp_f32
   ...     everything else is reported as 'other' with the instruction list, labelled by hand in
           DESIGN.md.
-Blocks are counted once each (both instances of the pair and the accumulate branches)."""
+Blocks are counted once each (both instances of the pair and the accumulate branches); the counts per
+block tell the pair's main path from the rare blocks the loop also holds (the backward's settle
+re-evaluation and inlined flush). The SALU and branch instructions are listed after the VALU ones."""
 import re
 import sys
 
@@ -42,17 +44,24 @@ def inner_loop(body):
                 cur[1] += ln
             else:
                 cur[2].append(ln)
+    # the walk's s_ff1 may sit in the header (a `while (mask)` loop) or in the latch (the pair taken at
+    # the loop's end for the next iteration): the first inner loop any of whose blocks holds it
+    bb = lambda name: name.lstrip(".").replace("LBB", "BB")  # noqa: E731
     hdr = None
-    for i, (name, comment, lines) in enumerate(blocks):
-        if any("s_ff1_i32_b64" in x for x in lines) and "Inner Loop Header" in comment:
-            hdr = name.lstrip(".").replace("LBB", "BB")
-            out = list(lines)
+    for name, comment, lines in blocks:
+        if not any("s_ff1_i32_b64" in x for x in lines):
+            continue
+        m = re.search(r"in Loop: Header=(BB\w+)", comment)
+        cand = bb(name) if "Inner Loop Header" in comment else m.group(1) if m else None
+        if cand and any(bb(n) == cand and "Inner Loop Header" in c for n, c, _ in blocks):
+            hdr = cand
             break
     if hdr is None:
         raise SystemExit("no s_ff1 loop found")
+    out = []
     for name, comment, lines in blocks:
-        if f"Header={hdr} " in comment + " " and name.lstrip(".").replace("LBB", "BB") != hdr:
-            out += lines
+        if bb(name) == hdr or f"Header={hdr} " in comment + " ":
+            out += [f"; block {name}"] + lines
     return out
 
 
@@ -64,29 +73,44 @@ EXP_CONST = ("0x3fb8aa3b", "0xcb400000", "0xbf317200", "0xb5bfbe8e", "0x3ab54ace
 def main():
     text = open(sys.argv[1]).read()
     loop = inner_loop(kernel_body(text, sys.argv[2]))
-    insts = [ln.strip() for ln in loop if ln.strip() and not ln.strip().startswith((";", ".", "/"))]
-    insts = [s for s in insts if not s.startswith(("s_waitcnt", ";;#"))]
+    insts, block_of, blk = [], {}, "?"
+    for ln in loop:
+        s = ln.strip()
+        if s.startswith("; block "):
+            blk = s[len("; block "):]
+        if not s or s.startswith((";", ".", "/", "s_waitcnt")):
+            continue
+        block_of[len(insts)] = blk
+        insts.append(s)
     units = {"valu": [], "salu": [], "lds": [], "vmem": [], "branch": []}
-    for s in insts:
+    per_block = {}
+    for i, s in enumerate(insts):
         op = s.split()[0]
-        if op.startswith(("s_cbranch", "s_branch")):
-            units["branch"].append(s)
-        elif op.startswith("ds_"):
-            units["lds"].append(s)
-        elif op.startswith(("global_", "buffer_", "flat_")):
-            units["vmem"].append(s)
-        elif op.startswith("s_"):
-            units["salu"].append(s)
-        elif op.startswith("v_"):
-            units["valu"].append(s)
+        u = ("branch" if op.startswith(("s_cbranch", "s_branch")) else "lds" if op.startswith("ds_")
+             else "vmem" if op.startswith(("global_", "buffer_", "flat_")) else "salu" if op.startswith("s_")
+             else "valu" if op.startswith("v_") else None)
+        if u:
+            per_block.setdefault(block_of[i], dict.fromkeys(units, 0))[u] += 1
+            units[u].append(s)
     exp = [s for s in units["valu"] if s.startswith(("v_exp_f32", "v_med3_f32", "v_lshl_add_u32"))
            or any(c in s for c in EXP_CONST) or re.match(r"v_fma_f32 \S+, \S+, \S+, 1\.0", s)]
     print(f"loop: {len(insts)} instructions")
     for u, v in units.items():
         print(f"  {u:6s} {len(v)}")
     print(f"  VALU in the exp statement: {len(exp)}")
+    print("per block (valu salu lds vmem branch):")
+    for b, c in per_block.items():
+        print(f"  {b:12s} " + " ".join(f"{c[u]:4d}" for u in units))
     print("VALU listing:")
     for s in units["valu"]:
+        print("   ", s)
+    # the scalar side of the walk (DESIGN.md §4's SALU table); branches listed with it, as they issue
+    # on the scalar unit too
+    print("SALU listing:")
+    for s in units["salu"]:
+        print("   ", s)
+    print("branch listing:")
+    for s in units["branch"]:
         print("   ", s)
 
 
