@@ -7,7 +7,9 @@ the Adam group order of scene/gaussian_model.py:586-612).
 
 Pinned by tests/golden/train.npz: the reference's own GaussianModel run on CPU
 (tests/golden/make_golden_train.py) -- Adam steps, densification statistics,
-densify_and_prune with stored noise, reset_opacity.
+densify_and_prune with stored noise, reset_opacity -- and by tests/golden/train_edges.npz
+(tests/golden/make_golden_train_edges.py): densify_and_prune without and with a screen size and
+`prune`, on a model with every class of Gaussian (tests/test_train_ref64.py).
 """
 from __future__ import annotations
 
@@ -73,10 +75,11 @@ def build_rotation(q):
 
 
 def densify_and_prune(model, m, v, xyz_accum, normal_accum, denom, max_radii, max_grad, min_opacity, extent,
-                      max_screen_size, max_grad_normal, percent_dense, noise, N=2, prune_only=False):
+                      max_screen_size, max_grad_normal, percent_dense, noise, N=2, prune_only=False, return_source=False):
     """densify_and_prune (gaussian_model.py:1025-1043) = densify_and_clone (:982-1023), then
     densify_and_split (:926-980), then the opacity / size prune; or `prune` (:1045-1053) when
-    prune_only. model / m / v: dicts name -> [P, w]; returns new (model, m, v)."""
+    prune_only. model / m / v: dicts name -> [P, w]; returns new (model, m, v), and with
+    return_source also the source map and the counts of r3dg_densify_and_prune."""
     names = list(model)
     P = model["xyz"].shape[0]
     scale = np.exp(model["scaling"]).astype(F)
@@ -128,6 +131,13 @@ def densify_and_prune(model, m, v, xyz_accum, normal_accum, denom, max_radii, ma
         zc = np.zeros((keep_c.sum() + ck.sum(), a.shape[1]), F)
         om[k] = np.concatenate([m[k][keep_o], zc]).astype(F)
         ov[k] = np.concatenate([v[k][keep_o], zc]).astype(F)
+    if return_source:
+        # source row of every kept original (what prune_points slices the statistics by), -1 for
+        # clones and children; counts = [originals kept, clones kept, split, split with children kept]
+        n_new = int(keep_c.sum() + ck.sum())
+        source = np.concatenate([np.nonzero(keep_o)[0], np.full(n_new, -1)]).astype(np.int32)
+        counts = [int(keep_o.sum()), int(keep_c.sum()), int(ns), int(keep_s.sum())]
+        return out, om, ov, source, counts
     return out, om, ov
 
 

@@ -356,7 +356,8 @@ extern "C" int r3dg_densify_and_prune(const r3dg_param_layout* L, const float* p
                                       int** out_source, int* P_new, int* counts, r3dg_stream_t stream) {
     if (int e = check_layout(L)) return e;
     R3DG_REQUIRE(args && alloc && out_param && out_exp_avg && out_exp_avg_sq && P_new, "densify: null argument");
-    R3DG_REQUIRE(args->prune_only || (args->N >= 1 && randn && xyz_accum && normal_accum && denom),
+    // an empty model (everything pruned earlier) has empty statistics: nothing is read from them
+    R3DG_REQUIRE(args->prune_only || (args->N >= 1 && randn && (L->P == 0 || (xyz_accum && normal_accum && denom))),
                  "densify: clone/split need N >= 1, the gradient statistics and a noise source");
     const int roles[4] = {L->xyz, L->scaling, L->rotation, L->opacity};
     const int need[4] = {3, 3, 4, 1};
