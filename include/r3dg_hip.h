@@ -475,6 +475,68 @@ int r3dg_densify_and_prune(const r3dg_param_layout* layout, const float* param, 
 int r3dg_reset_opacity(const r3dg_param_layout* layout, float* param, float* exp_avg, float* exp_avg_sq,
                        r3dg_stream_t stream);
 
+/* ---- parameter activations (scene/gaussian_model.py:23-44, 331-413, gaussian_renderer/neilf.py:102) ----
+ * Everything between the flat parameter buffer and the per-Gaussian inputs of the rasterizer, the render
+ * equation and the tracer, in at most two launches per direction. Forward, per Gaussian p (NULL output:
+ * skipped):
+ *   out_scaling [P,3] = expf(raw); out_rotation [P,4] = q / max(|q|, 1e-12); out_normal [P,3] = n /
+ *   max(|n|, 1e-3); out_opacity [P,1], out_base_color [P,3], out_roughness [P,1], out_metallic [P,1] =
+ *   1 / (1 + expf(-x)); out_shs [P,16,3], out_incidents [P,16,3], out_visibility [P,16,1]: row p of the dc
+ *   group followed by row p of the rest group (copies); out_viewdirs [P,3] = v / max(|v|, 1e-12), v = campos -
+ *   xyz; out_symm_inv [P,6] = get_inverse_covariance(): L = R(q^ / |q^|) diag(1 / s) of the activated q^, s
+ *   (build_rotation's own normalisation included), the upper triangle of L L^T in strip_symmetric's order.
+ * Every group of the layout must be named by exactly one role (xyz, scaling, rotation, opacity in the layout,
+ * the others here) with the widths 3, 3, 4, 1, normal 3, f_dc 3, f_rest 45, base_color 3, roughness 1,
+ * metallic 1, incidents_dc 3, incidents_rest 45, visibility_dc 1, visibility_rest 15; normal, f_dc and f_rest
+ * are required, the seven others are present together or all absent (-1). */
+typedef struct r3dg_activation_io {
+    size_t struct_size;               /* sizeof(r3dg_activation_io); checked */
+    const r3dg_param_layout* layout;
+    int normal, f_dc, f_rest;         /* group index of each role */
+    int base_color, roughness, metallic, incidents_dc, incidents_rest, visibility_dc, visibility_rest; /* or -1 */
+    const float* campos;              /* device, 3 floats; NULL: no viewdirs */
+    float *out_scaling, *out_rotation, *out_normal, *out_opacity, *out_shs;
+    float *out_base_color, *out_roughness, *out_metallic, *out_incidents, *out_visibility;
+    float* out_viewdirs;              /* needs campos */
+    float* out_symm_inv;              /* forward only: it has no gradient */
+} r3dg_activation_io;
+
+/* R3DG_ERR_ARG before any device work: a wrong struct_size, a layout that breaks the rule above, a NULL
+ * param with P > 0, out_viewdirs without campos. P == 0: R3DG_OK, nothing launched. No allocation, no
+ * atomics, no host synchronisation; every launch is on stream. */
+int r3dg_activate_forward(const r3dg_activation_io* io, const float* param, r3dg_stream_t stream);
+
+/* One upstream gradient: row p starts at ptr + p * stride floats and is dense (stride >= the row's width,
+ * so a column block of a wider row-major array passes as it is). ptr NULL: the gradient is zero. */
+typedef struct r3dg_grad_rows {
+    const float* ptr;
+    int64_t stride;
+} r3dg_grad_rows;
+
+typedef struct r3dg_activation_grads {
+    size_t struct_size;               /* sizeof(r3dg_activation_grads); checked */
+    r3dg_grad_rows xyz, scaling, rotation, normal, opacity, shs;      /* widths 3, 3, 4, 3, 1, 48 */
+    r3dg_grad_rows base_color, roughness, metallic, incidents, visibility; /* 3, 1, 1, 48, 16 */
+    r3dg_grad_rows viewdirs;          /* 3; needs io->campos */
+} r3dg_activation_grads;
+
+/* The gradient of every group into `grad`, laid out as param. With r = |x|, y = x / r and upstream g:
+ * normalise (normal eps 1e-3, rotation and viewdirs 1e-12): (g - y (y.g)) / r where r >= eps, else g / eps
+ * (torch's clamp_min mask, decided on the float32 norm; a zero vector gets g / eps); exp: g * out; sigmoid:
+ * g * s * (1 - s); the SH rows split into the dc and the rest row (copies); xyz: g_xyz - J(v)^T g_viewdirs.
+ * Two of these are evaluated more exactly than the float32 reference evaluates them, so results differ from
+ * it towards the exact value: the sigmoid slope s (1 - s) is computed as t / (1 + t)^2, t = expf(-|x|),
+ * which does not cancel at large |x| (float32 autograd gives 0 at x = 20, this gives 2.1e-9 g); the
+ * normalise projection, v = campos - xyz included, is computed in double from the float32 inputs and rounded
+ * to float32 once (in float32 it loses all digits where g is nearly parallel to x). Everything is recomputed from
+ * param: io's output pointers are not read, and param must be what the forward saw. accumulate == 0: every
+ * element of grad[0, P * sum(width)) is written, zeros where the upstream is NULL, and nothing behind it;
+ * accumulate != 0: the gradients are added to grad, and a NULL upstream leaves its group untouched.
+ * R3DG_ERR_ARG before any device work: a wrong struct_size of either struct, what r3dg_activate_forward
+ * refuses, a stride below the row's width, viewdirs without campos, an upstream of an absent role. */
+int r3dg_activate_backward(const r3dg_activation_io* io, const float* param, const r3dg_activation_grads* grads,
+                           float* grad, int accumulate, r3dg_stream_t stream);
+
 /* ---- BVH visibility tracer (reference module bvh_tracing._C,
  *      bvh/src/bindings.cpp:9-11) ------------------------------------------------------------
  * Tree layout (the reference's, bvh/__init__.py:31-37): nodes int32 [2P-1, 5] rows

@@ -21,6 +21,10 @@ light (gaussian_renderer/neilf_composite.py, scene/envmap.py).
 `relightable3dgaussian_amd.visibility` is visibility baking: the traced per-sample visibility that
 render equation reads (relighting.py `update_visibility`), the visibility-SH training term
 (neilf.py `lambda_visibility`) and `finetune_visibility` (scene/gaussian_model.py).
+
+`relightable3dgaussian_amd.activation` is the parameter activations of a training iteration
+(`GaussianTrainState.activate`): the getters of scene/gaussian_model.py and neilf.py's view
+directions from the flat parameter buffer, and their backward into the flat gradient buffer.
 """
 from __future__ import annotations
 

@@ -873,6 +873,113 @@ void reset_opacity(int64_t P, const std::vector<int64_t>& widths, const std::vec
           "reset_opacity");
 }
 
+// ---- parameter activations (relightable3dgaussian_amd/activation.py; csrc/activation.hip) ----------
+
+// role_groups: the group index of normal, f_dc, f_rest, base_color, roughness, metallic, incidents_dc,
+// incidents_rest, visibility_dc, visibility_rest (-1: absent)
+r3dg_activation_io make_activation_io(const r3dg_param_layout* L, const std::vector<int64_t>& role_groups,
+                                      const torch::Tensor& param, const std::optional<torch::Tensor>& campos,
+                                      torch::Tensor& campos_keep, const char* who) {
+    TORCH_CHECK(role_groups.size() == 10, who, ": role_groups holds 10 group indices");
+    TORCH_CHECK(param.is_cuda(), who, ": param must be a GPU tensor (this build has no CPU path)");
+    int64_t total = 0;
+    for (int g = 0; g < L->n_groups; ++g) total += (int64_t)L->P * L->width[g];
+    TORCH_CHECK(L->P >= 0 && param.numel() >= total, who, ": param holds fewer than P * sum(widths) floats");
+    f32_ptr(param, "param");
+    r3dg_activation_io io{};
+    io.struct_size = sizeof(io);
+    io.layout = L;
+    io.normal = (int)role_groups[0]; io.f_dc = (int)role_groups[1]; io.f_rest = (int)role_groups[2];
+    io.base_color = (int)role_groups[3]; io.roughness = (int)role_groups[4]; io.metallic = (int)role_groups[5];
+    io.incidents_dc = (int)role_groups[6]; io.incidents_rest = (int)role_groups[7];
+    io.visibility_dc = (int)role_groups[8]; io.visibility_rest = (int)role_groups[9];
+    if (campos.has_value()) {
+        TORCH_CHECK(campos->is_cuda() && campos->scalar_type() == torch::kFloat32 && campos->numel() == 3 &&
+                        campos->device() == param.device(),
+                    who, ": campos must be 3 float32 on param's device");
+        campos_keep = campos->contiguous();
+        io.campos = campos_keep.data_ptr<float>();
+    }
+    return io;
+}
+
+// -> [scaling, rotation, normal, opacity, shs, base_color, roughness, metallic, incidents, visibility,
+//     viewdirs, symm_inv]; None for the PBR outputs of a 7-group layout, viewdirs without campos, symm_inv
+//     when not asked for
+std::vector<std::optional<torch::Tensor>> activate_forward(int64_t P, const std::vector<int64_t>& widths,
+                                                           const std::vector<int64_t>& roles,
+                                                           const std::vector<int64_t>& role_groups,
+                                                           const torch::Tensor& param,
+                                                           const std::optional<torch::Tensor>& campos,
+                                                           bool inverse_covariance) {
+    const r3dg_param_layout L = make_layout(P, widths, roles);
+    torch::Tensor cp;
+    r3dg_activation_io io = make_activation_io(&L, role_groups, param, campos, cp, "activate_forward");
+    const c10::OptionalDeviceGuard guard(param.device());
+    const auto fopt = param.options();
+    const bool pbr = io.base_color >= 0;
+    std::vector<std::optional<torch::Tensor>> out(12);
+    auto make = [&](int slot, std::vector<int64_t> shape, bool on) -> float* {
+        if (!on) return nullptr;
+        shape.insert(shape.begin(), P);
+        out[slot] = torch::empty(shape, fopt);
+        return out[slot]->data_ptr<float>();
+    };
+    io.out_scaling = make(0, {3}, true); io.out_rotation = make(1, {4}, true); io.out_normal = make(2, {3}, true);
+    io.out_opacity = make(3, {1}, true); io.out_shs = make(4, {16, 3}, true);
+    io.out_base_color = make(5, {3}, pbr); io.out_roughness = make(6, {1}, pbr); io.out_metallic = make(7, {1}, pbr);
+    io.out_incidents = make(8, {16, 3}, pbr); io.out_visibility = make(9, {16, 1}, pbr);
+    io.out_viewdirs = make(10, {3}, campos.has_value()); io.out_symm_inv = make(11, {6}, inverse_covariance);
+    check(r3dg_activate_forward(&io, param.data_ptr<float>(), stream_of(param.device())), "activate_forward");
+    return out;
+}
+
+// upstreams: [xyz, scaling, rotation, normal, opacity, shs, base_color, roughness, metallic, incidents,
+// visibility, viewdirs], None = zero. An upstream whose dimensions behind the first are dense (a column block
+// of a wider row-major array) is passed with its stride(0); any other layout is made contiguous first.
+void activate_backward(int64_t P, const std::vector<int64_t>& widths, const std::vector<int64_t>& roles,
+                       const std::vector<int64_t>& role_groups, const torch::Tensor& param,
+                       const std::optional<torch::Tensor>& campos,
+                       const std::vector<std::optional<torch::Tensor>>& upstreams, torch::Tensor grad,
+                       bool accumulate) {
+    const char* who = "activate_backward";
+    const r3dg_param_layout L = make_layout(P, widths, roles);
+    torch::Tensor cp;
+    const r3dg_activation_io io = make_activation_io(&L, role_groups, param, campos, cp, who);
+    TORCH_CHECK(upstreams.size() == 12, who, ": 12 upstream slots");
+    TORCH_CHECK(grad.is_cuda() && grad.device() == param.device() && grad.numel() >= param.numel(), who,
+                ": grad must be a buffer of param's size on param's device");
+    f32_ptr(grad, "grad");
+    const c10::OptionalDeviceGuard guard(param.device());
+    r3dg_activation_grads g{};
+    g.struct_size = sizeof(g);
+    r3dg_grad_rows* slots[12] = {&g.xyz, &g.scaling, &g.rotation, &g.normal, &g.opacity, &g.shs, &g.base_color,
+                                 &g.roughness, &g.metallic, &g.incidents, &g.visibility, &g.viewdirs};
+    const int64_t width[12] = {3, 3, 4, 3, 1, 48, 3, 1, 1, 48, 16, 3};
+    std::vector<torch::Tensor> keep;
+    for (int i = 0; i < 12; ++i) {
+        if (!upstreams[i].has_value()) continue;
+        torch::Tensor t = *upstreams[i];
+        TORCH_CHECK(t.is_cuda() && t.device() == param.device() && t.scalar_type() == torch::kFloat32, who,
+                    ": upstream ", i, " must be a float32 tensor on param's device");
+        TORCH_CHECK(t.dim() >= 1 && t.size(0) == P && t.numel() == P * width[i], who, ": upstream ", i,
+                    " must be [P, ...] with ", width[i], " floats per row");
+        // dense behind the first dimension, rows at least a row apart
+        bool dense = t.stride(0) >= width[i];
+        int64_t expect = 1;
+        for (int64_t d = t.dim() - 1; d >= 1; --d) {
+            if (t.size(d) != 1 && t.stride(d) != expect) dense = false;
+            expect *= t.size(d);
+        }
+        if (!dense) t = t.contiguous();
+        keep.push_back(t);
+        if (P > 0) *slots[i] = r3dg_grad_rows{t.data_ptr<float>(), P == 1 ? width[i] : t.stride(0)};
+    }
+    check(r3dg_activate_backward(&io, param.data_ptr<float>(), &g, grad.data_ptr<float>(), accumulate ? 1 : 0,
+                                 stream_of(param.device())),
+          who);
+}
+
 // ---- BVH visibility tracer: the reference's bvh_tracing._C (bvh/src/bindings.cpp:9-11) ----------
 
 torch::Tensor cuda_f32(const torch::Tensor& t, const char* what) {
@@ -1484,6 +1591,13 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("densification_stats", &densification_stats);
     m.def("densify_and_prune", &densify_and_prune);
     m.def("reset_opacity", &reset_opacity);
+    // parameter activations (relightable3dgaussian_amd/activation.py)
+    m.def("activate_forward", &activate_forward, py::arg("P"), py::arg("widths"), py::arg("roles"),
+          py::arg("role_groups"), py::arg("param"), py::arg("campos") = py::none(),
+          py::arg("inverse_covariance") = false);
+    m.def("activate_backward", &activate_backward, py::arg("P"), py::arg("widths"), py::arg("roles"),
+          py::arg("role_groups"), py::arg("param"), py::arg("campos"), py::arg("upstreams"), py::arg("grad"),
+          py::arg("accumulate") = false);
     // BVH visibility tracer (§8f rank 4): the reference's bvh_tracing._C names + the leaf boxes
     m.def("create_bvh", &create_bvh);
     m.def("trace_bvh", &trace_bvh);

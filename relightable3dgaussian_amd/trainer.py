@@ -164,6 +164,14 @@ class GaussianTrainState:
     def grad_view(self, name):
         return self._view(self.grad, name)
 
+    def activate(self, campos=None, inverse_covariance: bool = False, accumulate: bool = False):
+        """The reference's getters (get_scaling, get_rotation, get_normal, get_opacity, get_shs, ...,
+        gaussian_model.py:331-413) and neilf.py:102's view directions in two launches; `backward()`
+        through the outputs writes every group's gradient into `self.grad` (activation.py)."""
+        from .activation import activate
+
+        return activate(self, campos=campos, inverse_covariance=inverse_covariance, accumulate=accumulate)
+
     # ---- gaussian_model.py:658-793 (PLY checkpoints) -------------------------------------------
     @staticmethod
     def load_ply(path: str, device="cuda", use_pbr: bool = True, max_sh_degree: int = 3, **kw):
