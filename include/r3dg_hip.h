@@ -537,6 +537,85 @@ typedef struct r3dg_activation_grads {
 int r3dg_activate_backward(const r3dg_activation_io* io, const float* param, const r3dg_activation_grads* grads,
                            float* grad, int accumulate, r3dg_stream_t stream);
 
+/* ---- scene composition and the points capture (relighting.py:31-55, 89-123; scene/gaussian_model.py:237-262
+ *      set_transform, :464-476 create_from_gaussians; utils/general_utils.py:105-149) -----------------------
+ * A transform is 19 floats on the device, xform = M (4x4, row-major) followed by c (3), and a flag word that
+ * says what of them applies. Vectors are columns: x' = M[:3,:3] x + M[:3,3].
+ *   R3DG_XF_TRANSFORM (alone)  set_transform(transform=M): A = M[:3,:3], t = M[:3,3], s[i] = |row i of A|,
+ *       R = A with row i divided by s[i], q_T = rotation_to_quaternion(R) = normalize((qw, (R21 - R12) / 4qw,
+ *       (R02 - R20) / 4qw, (R10 - R01) / 4qw)), qw = sqrt(max(1 + R00 + R11 + R22, 1e-7)) / 2. Per Gaussian:
+ *       scaling[j] <- expf(scaling[j]) * s[j] (the raw group stores its logf); xyz <- A xyz + t; normal <- R normal;
+ *       rotation <- quaternion_multiply(q_T, rotation), not normalised. M's last row and c are not read,
+ *       so the 16 floats of a 4x4 may be passed as they are.
+ *   otherwise any of, applied in this order (the reference's):
+ *   R3DG_XF_CENTER    xyz <- xyz - c
+ *   R3DG_XF_ROTATION  R = M[:3,:3]: xyz <- R xyz, normal <- R normal, rotation <- q_R x rotation
+ *   R3DG_XF_SCALE     s = M[3,0:3]: xyz <- xyz * s, scaling[j] <- expf(scaling[j]) * s[j]
+ *   R3DG_XF_OFFSET    xyz <- xyz + M[:3,3]
+ * s, R and the quaternion are uniform over a launch and computed in the kernel; every operation rounds on its
+ * own, sums run left to right. The quaternion formula is ill-conditioned where 1 + trace(R) is small, as the
+ * reference's is. The SH groups are NOT rotated (the reference rotates none either). flags == 0: no transform. */
+#define R3DG_XF_TRANSFORM 1
+#define R3DG_XF_CENTER 2
+#define R3DG_XF_ROTATION 4
+#define R3DG_XF_SCALE 8
+#define R3DG_XF_OFFSET 16
+
+/* set_transform in place on the flat parameter buffer, one launch: the groups layout->xyz, layout->scaling,
+ * layout->rotation and `normal` (widths 3, 3, 4, 3) are rewritten (a group only when the flags touch it), every
+ * other group, everything behind P * sum(width) and the Adam moments are not touched. Any number of groups
+ * (7 or 14). R3DG_ERR_ARG before any device work: a bad layout, a role outside it or of the wrong width, unknown
+ * flags, R3DG_XF_TRANSFORM with another flag, flags without xform. P == 0 or flags == 0: nothing launched. */
+int r3dg_set_transform(const r3dg_param_layout* layout, int normal, float* param, const float* xform, int flags,
+                       r3dg_stream_t stream);
+
+/* The composite's arrays, each contiguous [P_total, ...] float32; an object writes rows [row, row + P). */
+typedef struct r3dg_compose_out {
+    size_t struct_size;  /* sizeof(r3dg_compose_out); checked */
+    float *xyz;          /* [.,3]    moved */
+    float *scaling;      /* [.,3]    expf(raw) * s: the reference's exp(log(exp(raw) * s)) within a few ulp */
+    float *rotation;     /* [.,4]    (q_T x raw) / max(|.|, 1e-12) */
+    float *normal;       /* [.,3]    (R raw) / max(|.|, 1e-3) */
+    float *opacity, *base_color, *roughness, *metallic; /* [.,1] [.,3] [.,1] [.,1]  1 / (1 + expf(-raw)) */
+    float *shs;          /* [.,16,3] row of f_dc, then row of f_rest */
+    float *incidents;    /* [.,16,3] zeros (relighting.py:52-53) */
+    float *visibility_dc;   /* [.,1,1]  raw copy */
+    float *visibility_rest; /* [.,24,1] raw copy of the 15, then 9 zeros (relighting.py:46-50) */
+    float *symm_inv;     /* [.,6]    get_inverse_covariance() of the moved Gaussian as r3dg_activate_forward
+                                     computes it from the rotation and scaling above; NULL: skipped */
+} r3dg_compose_out;
+
+/* One object of scene_composition: reads the 14-group flat buffer `param` of io->layout (io names the roles as
+ * for r3dg_activate_forward; its campos and output pointers are not read), applies the transform and the
+ * activations with the device functions of r3dg_set_transform and r3dg_activate_forward, and writes rows
+ * [row, row + P) of the composite. Two launches (the per-Gaussian groups; the wide SH rows as coalesced
+ * copies); param is read-only and nothing else is allocated or written. The output row blocks may start at any
+ * 4-byte-aligned address. R3DG_ERR_ARG before any device work: what r3dg_activate_forward refuses in io, a
+ * 7-group layout, bad flags, a wrong struct_size, row < 0, a NULL array other than symm_inv (also with P == 0),
+ * a NULL param with P > 0. P == 0: nothing launched. The caller guarantees row + P rows in every array. */
+int r3dg_compose_object(const r3dg_activation_io* io, const float* param, const float* xform, int flags,
+                        const r3dg_compose_out* out, int64_t row, r3dg_stream_t stream);
+
+/* render_points (relighting.py:89-123), the z-buffered point cloud, without its loop. world_view is the
+ * reference's transposed [4,4] (16 floats) and intrinsics [3,3] (9), both on the device. The background is bg,
+ * 3 floats on the device, or, when bg is NULL, the 3 host floats bg_value, passed to the kernel by value (no
+ * copy). Per point i:
+ *   (xc, yc, z) = the first three components of [x, y, z, 1] @ world_view;  (uh, vh, wh) = K (xc, yc, z);
+ *   u = uh / wh, v = vh / wh (wh is z bit for bit when K's last row is (0, 0, 1));
+ *   dropped when u or v is not finite (this covers z == 0, where the reference's .long() is undefined);
+ *   px = trunc(u), py = trunc(v), toward zero as .long(): a coordinate in (-1, 0) lands in column / row 0;
+ *   a candidate when 0 <= px < W, 0 <= py < H and z < 10000 (the reference's initial depth, strict).
+ * There is no near plane, as in the reference: a point behind the camera takes part with its negative z and
+ * beats every point in front. Every pixel takes color[i] of its candidate with the smallest z, the smallest i
+ * among bit-equal z (the reference's two scatters leave that case undefined), bg where it has none;
+ * out_rgb is [3,H,W], out_depth (may be NULL) [H,W] with 10000 at empty pixels. Deterministic and
+ * bit-reproducible. Scratch: H * W 64-bit keys (order-preserving bits of z : i) from scratch_alloc, cleared by
+ * a memset; one pass of one global 64-bit atomic min per candidate (skipped when a plain load shows that the
+ * key already loses); one resolve pass. No loop, no host synchronisation. H * W < 2^31. */
+int r3dg_render_points(int P, const float* xyz, const float* color, const float* world_view,
+                       const float* intrinsics, int H, int W, const float* bg, const float* bg_value, float* out_rgb,
+                       float* out_depth, r3dg_alloc_fn scratch_alloc, void* scratch_ctx, r3dg_stream_t stream);
+
 /* ---- BVH visibility tracer (reference module bvh_tracing._C,
  *      bvh/src/bindings.cpp:9-11) ------------------------------------------------------------
  * Tree layout (the reference's, bvh/__init__.py:31-37): nodes int32 [2P-1, 5] rows

@@ -25,6 +25,10 @@ render equation reads (relighting.py `update_visibility`), the visibility-SH tra
 `relightable3dgaussian_amd.activation` is the parameter activations of a training iteration
 (`GaussianTrainState.activate`): the getters of scene/gaussian_model.py and neilf.py's view
 directions from the flat parameter buffer, and their backward into the flat gradient buffer.
+
+`relightable3dgaussian_amd.compose` is the relighting script's scene composition (`set_transform`,
+`compose_scene`, `load_scene`: relighting.py `scene_composition`), and `relight.render_points` its
+`points` capture.
 """
 from __future__ import annotations
 

@@ -27,7 +27,7 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
 HIP_SOURCES = ["preprocess.hip", "render_fwd.hip", "render_bwd.hip", "brdf.hip", "shaders.hip", "rasterizer.hip",
                "optim.hip", "bvh.hip", "knn.hip", "loss.hip", "reg_loss.hip", "relight.hip", "visibility.hip",
-               "activation.hip"]
+               "activation.hip", "compose.hip"]
 HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-result",
              "-munsafe-fp-atomics", f"-I{INC}", f"-I{CSRC}"]
 # the key path (projection, radius, rect) must not contract a*b+c into fma: see preprocess.hip
@@ -54,8 +54,11 @@ HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-W
 # (csrc/sh_dirs.h is shared with bvh.hip and relight.hip, both uncontracted as well)
 # activation.hip: its float32 reference is the getters' torch tensor code, which rounds every operation (the
 # squared norms, the rotation matrix, L L^T and the normalise gradient's projection stay uncontracted)
+# compose.hip: the same reason and the same device functions (csrc/act_device.h): its reference is set_transform's
+# and the getters' torch tensor code, and a composed activation must have activation.hip's bits
 PER_FILE_FLAGS = {"preprocess.hip": ["-ffp-contract=off"], "bvh.hip": ["-ffp-contract=off"],
                   "visibility.hip": ["-ffp-contract=off"], "activation.hip": ["-ffp-contract=off"],
+                  "compose.hip": ["-ffp-contract=off"],
                   "knn.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
                   "reg_loss.hip": ["-ffp-contract=off"], "relight.hip": ["-ffp-contract=off"],
                   "brdf.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],

@@ -980,6 +980,123 @@ void activate_backward(int64_t P, const std::vector<int64_t>& widths, const std:
           who);
 }
 
+// ---- scene composition and the points capture (relightable3dgaussian_amd/compose.py; csrc/compose.hip) ----
+
+// the 19 floats of a transform on param's device (None with flags == 0)
+const float* xform_ptr(const std::optional<torch::Tensor>& xform, int64_t flags, const torch::Tensor& param,
+                       const char* who) {
+    if (!xform.has_value()) {
+        TORCH_CHECK(flags == 0, who, ": transform flags without the 19 floats");
+        return nullptr;
+    }
+    TORCH_CHECK(xform->is_cuda() && xform->device() == param.device() && xform->scalar_type() == torch::kFloat32 &&
+                    xform->is_contiguous() &&
+                    (xform->numel() == 19 || (xform->numel() == 16 && flags == R3DG_XF_TRANSFORM)),
+                who, ": xform must be 19 contiguous float32 on param's device (16 do for a full transform)");
+    return xform->data_ptr<float>();
+}
+
+void set_transform(int64_t P, const std::vector<int64_t>& widths, const std::vector<int64_t>& roles,
+                   int64_t normal_group, torch::Tensor param, const std::optional<torch::Tensor>& xform,
+                   int64_t flags) {
+    const char* who = "set_transform";
+    const r3dg_param_layout L = make_layout(P, widths, roles);
+    f32_ptr(param, "set_transform: param");
+    int64_t total = 0;
+    for (int g = 0; g < L.n_groups; ++g) total += (int64_t)L.P * L.width[g];
+    TORCH_CHECK(L.P >= 0 && param.numel() >= total, who, ": param holds fewer than P * sum(widths) floats");
+    const float* xf = xform_ptr(xform, flags, param, who);
+    const c10::OptionalDeviceGuard guard(param.device());
+    check(r3dg_set_transform(&L, (int)normal_group, param.data_ptr<float>(), xf, (int)flags,
+                             stream_of(param.device())),
+          who);
+}
+
+// outs: [xyz, scaling, rotation, normal, opacity, base_color, roughness, metallic, shs, incidents, visibility_dc,
+// visibility_rest, symm_inv (None: skipped)], the composite's arrays; the object writes rows [row, row + P)
+void compose_object(int64_t P, const std::vector<int64_t>& widths, const std::vector<int64_t>& roles,
+                    const std::vector<int64_t>& role_groups, const torch::Tensor& param,
+                    const std::optional<torch::Tensor>& xform, int64_t flags,
+                    const std::vector<std::optional<torch::Tensor>>& outs, int64_t row) {
+    const char* who = "compose_object";
+    const r3dg_param_layout L = make_layout(P, widths, roles);
+    torch::Tensor cp;
+    const r3dg_activation_io io = make_activation_io(&L, role_groups, param, std::nullopt, cp, who);
+    const float* xf = xform_ptr(xform, flags, param, who);
+    TORCH_CHECK(outs.size() == 13, who, ": 13 output slots");
+    TORCH_CHECK(row >= 0, who, ": negative row offset");
+    const int64_t width[13] = {3, 3, 4, 3, 1, 3, 1, 1, 48, 48, 1, 24, 6};
+    float* ptr[13];
+    for (int i = 0; i < 13; ++i) {
+        ptr[i] = nullptr;
+        if (!outs[i].has_value()) {
+            TORCH_CHECK(i == 12, who, ": only symm_inv may be None");
+            continue;
+        }
+        const torch::Tensor& t = *outs[i];
+        TORCH_CHECK(t.is_cuda() && t.device() == param.device() && t.scalar_type() == torch::kFloat32 &&
+                        t.is_contiguous(),
+                    who, ": output ", i, " must be a contiguous float32 tensor on param's device");
+        TORCH_CHECK(t.numel() >= (row + P) * width[i], who, ": output ", i, " holds fewer than row + P rows");
+        ptr[i] = t.data_ptr<float>();
+    }
+    r3dg_compose_out o{};
+    o.struct_size = sizeof(o);
+    o.xyz = ptr[0]; o.scaling = ptr[1]; o.rotation = ptr[2]; o.normal = ptr[3]; o.opacity = ptr[4];
+    o.base_color = ptr[5]; o.roughness = ptr[6]; o.metallic = ptr[7]; o.shs = ptr[8]; o.incidents = ptr[9];
+    o.visibility_dc = ptr[10]; o.visibility_rest = ptr[11]; o.symm_inv = ptr[12];
+    const c10::OptionalDeviceGuard guard(param.device());
+    check(r3dg_compose_object(&io, param.data_ptr<float>(), xf, (int)flags, &o, row, stream_of(param.device())), who);
+}
+
+// bg: 3 floats on the device, or None with the 3 host numbers bg_value (passed to the kernel by value)
+// -> (rgb [3,H,W], depth [H,W] or None)
+std::tuple<torch::Tensor, std::optional<torch::Tensor>> render_points(const torch::Tensor& xyz,
+                                                                      const torch::Tensor& color,
+                                                                      const torch::Tensor& world_view,
+                                                                      const torch::Tensor& intrinsics, int64_t H,
+                                                                      int64_t W,
+                                                                      const std::optional<torch::Tensor>& bg,
+                                                                      const std::vector<double>& bg_value,
+                                                                      bool return_depth) {
+    const char* who = "render_points";
+    const torch::Device dev = xyz.device();
+    auto dev_f32 = [&](const torch::Tensor& t, int64_t n, const char* name) {
+        TORCH_CHECK(t.is_cuda() && t.device() == dev && t.scalar_type() == torch::kFloat32, who, ": ", name,
+                    " must be a float32 tensor on xyz's GPU device (this build has no CPU path)");
+        TORCH_CHECK(n < 0 || t.numel() == n, who, ": ", name, " must hold ", n, " floats");
+        return t.contiguous();
+    };
+    TORCH_CHECK(xyz.dim() == 2 && xyz.size(1) == 3 && color.dim() == 2 && color.size(1) == 3 &&
+                    color.size(0) == xyz.size(0),
+                who, ": xyz and color must be [P, 3]");
+    TORCH_CHECK(H > 0 && W > 0 && H * W <= 0x7fffffffLL, who, ": bad H or W");
+    TORCH_CHECK(xyz.size(0) <= 0x7fffffffLL, who, ": more than 2^31 - 1 points (a pixel's key holds a 32-bit index)");
+    const auto x = dev_f32(xyz, -1, "xyz"), c = dev_f32(color, -1, "color");
+    const auto v = dev_f32(world_view, 16, "world_view_transform"), k = dev_f32(intrinsics, 9, "intrinsics");
+    torch::Tensor b;
+    float bgv[3] = {0.0f, 0.0f, 0.0f};
+    if (bg.has_value()) {
+        b = dev_f32(*bg, 3, "bg");
+    } else {
+        TORCH_CHECK(bg_value.size() == 3, who, ": bg_value must hold 3 numbers");
+        for (int i = 0; i < 3; ++i) bgv[i] = (float)bg_value[i];
+    }
+    const c10::OptionalDeviceGuard guard(dev);
+    torch::Tensor rgb = torch::empty({3, H, W}, xyz.options());
+    std::optional<torch::Tensor> depth;
+    if (return_depth) depth = torch::empty({H, W}, xyz.options());
+    const int64_t P = xyz.size(0);
+    auto bopt = torch::TensorOptions().dtype(torch::kUInt8).device(dev);
+    TensorAlloc scratch{bopt, torch::empty({0}, bopt)};
+    check(r3dg_render_points((int)P, P ? x.data_ptr<float>() : nullptr, P ? c.data_ptr<float>() : nullptr,
+                             v.data_ptr<float>(), k.data_ptr<float>(), (int)H, (int)W,
+                             bg.has_value() ? b.data_ptr<float>() : nullptr, bgv, rgb.data_ptr<float>(), depth ? depth->data_ptr<float>() : nullptr, tensor_alloc, &scratch,
+                             stream_of(dev)),
+          who);
+    return {rgb, depth};
+}
+
 // ---- BVH visibility tracer: the reference's bvh_tracing._C (bvh/src/bindings.cpp:9-11) ----------
 
 torch::Tensor cuda_f32(const torch::Tensor& t, const char* what) {
@@ -1598,6 +1715,10 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.def("activate_backward", &activate_backward, py::arg("P"), py::arg("widths"), py::arg("roles"),
           py::arg("role_groups"), py::arg("param"), py::arg("campos"), py::arg("upstreams"), py::arg("grad"),
           py::arg("accumulate") = false);
+    // scene composition and the points capture (relightable3dgaussian_amd/compose.py, relight.render_points)
+    m.def("set_transform", &set_transform);
+    m.def("compose_object", &compose_object);
+    m.def("render_points", &render_points);
     // BVH visibility tracer (§8f rank 4): the reference's bvh_tracing._C names + the leaf boxes
     m.def("create_bvh", &create_bvh);
     m.def("trace_bvh", &trace_bvh);

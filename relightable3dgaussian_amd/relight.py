@@ -16,6 +16,9 @@ chunk loop over `rendering_equation_python` and the `torch.cat` of nine tensors
   visibility  the baked visibility SH [P, S, 1], read when `bake` is true
   bake=False  the per-sample traced visibility `visibility_precompute` [P, Ns] or [P, Ns, 1]
               (pc._visibility_tracing); without it a ValueError, as the reference raises
+`render_points(xyz, color, world_view_transform, intrinsics, H, W, bg, return_depth=False)` is the script's
+`points` capture (relighting.py:89-123), a z-buffered point cloud (csrc/compose.hip `r3dg_render_points`).
+
 Each SH width is 0..25. Forward only: the relighting script runs under torch.no_grad(). No CPU path and
 no torch fallback: the extension rejects CPU tensors.
 """
@@ -75,3 +78,28 @@ def render_equation_relight(base_color, roughness, metallic, normals, viewdirs, 
     extra_results = {k: cols[k] for k in ["incident_lights", "local_incident_lights", "global_incident_lights",
                                           "incident_visibility"]}
     return cols["rgb"], extra_results, features
+
+
+@torch.no_grad()
+def render_points(xyz, color, world_view_transform, intrinsics, H, W, bg, return_depth: bool = False):
+    """The `points` capture (relighting.py:89-123): the z-buffered point cloud -> [3, H, W], with
+    return_depth=True also the [H, W] depth (10000 at empty pixels). `world_view_transform` is the reference's
+    (transposed) [4, 4], `intrinsics` [3, 3], `bg` a number or [3]. One 64-bit atomic min per point and a resolve
+    pass in place of the reference's loop; no host synchronisation.
+
+    A point is projected as the reference does, operation for operation, dropped when its pixel coordinates
+    are not finite (z == 0), truncated toward zero as `.long()` (so a coordinate in (-1, 0) lands in column /
+    row 0), and kept when it lands inside the image with z < 10000. There is NO near plane, as in the reference:
+    a point behind the camera takes part with its negative z and wins its pixel. Every pixel shows its point
+    with the smallest z, the smallest index among equal z (the reference leaves that case undefined)."""
+    # a background on the device is read there; a host value goes to the kernel by value (no copy)
+    bg_dev, bg_value = None, []
+    if isinstance(bg, torch.Tensor) and bg.device.type != "cpu":
+        bg_dev = bg.detach().to(dtype=torch.float32).reshape(-1)
+        bg_dev = (bg_dev.expand(3) if bg_dev.numel() == 1 else bg_dev).contiguous()
+    else:
+        bg_value = [float(v) for v in torch.as_tensor(bg, dtype=torch.float32).reshape(-1).tolist()]
+        bg_value = bg_value * 3 if len(bg_value) == 1 else bg_value
+    rgb, depth = _C.render_points(xyz, color, world_view_transform, intrinsics, int(H), int(W), bg_dev, bg_value,
+                                  bool(return_depth))
+    return (rgb, depth) if return_depth else rgb

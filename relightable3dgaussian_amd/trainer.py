@@ -172,6 +172,15 @@ class GaussianTrainState:
 
         return activate(self, campos=campos, inverse_covariance=inverse_covariance, accumulate=accumulate)
 
+    def set_transform(self, rotation=None, center=None, scale=None, offset=None, transform=None):
+        """set_transform (gaussian_model.py:237-262) in place on the flat buffer, one kernel launch (after the
+        arguments are packed into 19 floats on the device, compose.pack_transform): `transform`
+        [4,4], or `center`, `rotation` [3,3], `scale` (number or [3]) and `offset` in the reference's order.
+        xyz, scaling, rotation and normal move; the SH groups are not rotated, as in the reference (compose.py)."""
+        from .compose import set_transform
+
+        set_transform(self, rotation=rotation, center=center, scale=scale, offset=offset, transform=transform)
+
     # ---- gaussian_model.py:658-793 (PLY checkpoints) -------------------------------------------
     @staticmethod
     def load_ply(path: str, device="cuda", use_pbr: bool = True, max_sh_degree: int = 3, **kw):
