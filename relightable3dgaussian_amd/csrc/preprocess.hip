@@ -406,12 +406,14 @@ __global__ void __launch_bounds__(1024) bin_colscan_kernel(BinArgs a, uint2* __r
 // instance count (bucket = count / 4, capped; descending). Only the schedule depends on the order,
 // so the order within a bucket, which LDS atomics leave unspecified, changes no result (measured:
 // exact-count buckets, which scatter the tiles of a bucket spatially, slowed the backward by 3 %).
-// One 1024-thread workgroup; the padded grid's last slots name no tile (T).
+// One 1024-thread workgroup; the padded grid's last slots name no tile (T). The caller gives the LDS:
+// hist[kTileOrderBuckets] and s_wave[16] (bin_scatter_kernel from its dynamic LDS: a __shared__ array here
+// would be static LDS of every kernel this is inlined into, on top of bin_lds_bytes; r3dg_kernels.h).
+constexpr int kTileOrderBuckets = 1024;
 __device__ __forceinline__ uint32_t block_exclusive_scan_1024(uint32_t v, uint32_t* s_wave);
-__device__ void tile_order_block(int T, const uint2* __restrict__ ranges, uint32_t* __restrict__ order) {
-    constexpr int NBK = 1024;
-    __shared__ uint32_t hist[NBK];
-    __shared__ uint32_t s_wave[16];
+__device__ __forceinline__ void tile_order_block(int T, const uint2* __restrict__ ranges,
+                                                 uint32_t* __restrict__ order, uint32_t* hist, uint32_t* s_wave) {
+    constexpr int NBK = kTileOrderBuckets;
     const int t = threadIdx.x;
     const int per = (T + 1023) / 1024;
     const int b0 = min(t * per, T), b1 = min(b0 + per, T);
@@ -439,7 +441,9 @@ __device__ void tile_order_block(int T, const uint2* __restrict__ ranges, uint32
 // tile_order_block on its own, when the LDS binning scattered nothing (no instances)
 __global__ void __launch_bounds__(1024) tile_order_kernel(int T, const uint2* __restrict__ ranges,
                                                           uint32_t* __restrict__ order) {
-    tile_order_block(T, ranges, order);
+    __shared__ uint32_t hist[kTileOrderBuckets];
+    __shared__ uint32_t s_wave[16];
+    tile_order_block(T, ranges, order, hist, s_wave);
 }
 
 // The scatter grid has one workgroup more than the binning's: it computes the tiles' longest-first
@@ -447,14 +451,16 @@ __global__ void __launch_bounds__(1024) tile_order_kernel(int T, const uint2* __
 // kernel 14.9 -> 11.5 us). (Every scatter workgroup scanning the tile counts itself, so that no
 // ranges kernel runs at all, measured slower: the scatter 69 -> 80 us, and the host, which must
 // allocate the binning state between the count readback and the scatter launch, then left the GPU
-// idle 6 us; profiles/r06/README.md.)
+// idle 6 us; profiles/r06/README.md.) The order workgroup's kTileOrderBuckets + 16 words are the first of
+// the kernel's dynamic LDS (bin_lds_bytes(T) >= 16 KiB at any T; it returns before the binning's use of
+// s_dyn), so the kernel has no static LDS and bin_lds_bytes is all it takes (r3dg_kernels.h).
 __global__ void __launch_bounds__(kBinThreads) bin_scatter_kernel(BinArgs a, const uint2* __restrict__ ranges,
                                                                   uint32_t* __restrict__ order) {
+    extern __shared__ uint32_t s_dyn[];
     if ((int)blockIdx.x == a.nblk) {
-        tile_order_block(a.T, ranges, order);
+        tile_order_block(a.T, ranges, order, s_dyn, s_dyn + kTileOrderBuckets);
         return;
     }
-    extern __shared__ uint32_t s_dyn[];
     uint32_t* s_pos = s_dyn;  // [T] next position of this workgroup's instances of each tile (bucket)
     uint32_t* s_end = s_dyn + a.T;
     int* s_x0 = reinterpret_cast<int*>(s_end + kBinSub);
@@ -550,6 +556,7 @@ __global__ void __launch_bounds__(256) bin_atomic_kernel(BinArgs a) {
 }
 
 static size_t bin_lds_bytes(int T) { return sizeof(uint32_t) * ((size_t)T + 4 * kBinSub); }
+static_assert(kTileOrderBuckets + 16 <= 4 * kBinSub, "bin_scatter_kernel's order workgroup: inside the dynamic LDS");
 
 // dynamic LDS above 64 KiB must be allowed per kernel (T > 12288 tiles, e.g. 4K frames)
 template <class K>

@@ -69,6 +69,15 @@ constexpr int kBinBucketShift = 28;  // the tile's index in its bucket above the
 constexpr int kBinThreads = 1024;                  // binning workgroup (one per CU)
 constexpr int kBinSub = 1024;                      // Gaussians staged in LDS at a time
 constexpr int kBinMaxTiles = (163840 - 16 * kBinSub) / 4;  // LDS counters per workgroup (160 KiB)
+// LDS invariant. bin_count_kernel and bin_scatter_kernel take bin_lds_bytes(T) = 4 (T + 4 kBinSub) bytes of
+// DYNAMIC LDS: the CU's whole 160 KiB at kBinMaxTiles tiles, and exactly the 64 KiB a launch may have without
+// hipFuncAttributeMaxDynamicSharedMemorySize at 12288 tiles (allow_lds raises the limit from the dynamic bytes
+// alone). So both kernels must have NO static LDS (.group_segment_fixed_size == 0): a __shared__ array in
+// them, or in a device function inlined into them, makes the launch unplaceable at the last LDS tile counts
+// and puts it over the unraised limit just below 12288 tiles (the order workgroup's 4160 B once did: at
+// 35825..36864 and 11249..12288 tiles; it now borrows its words from the dynamic LDS).
+// tests/test_binning_plan.py reads the static size from the built code objects.
+static_assert(4 * (kBinMaxTiles + 4 * kBinSub) <= 163840, "bin_lds_bytes(kBinMaxTiles) exceeds one CU's LDS");
 // binning workgroups for T tiles: the [nblk, T] count matrix stays <= kBinMatrix entries
 constexpr int kBinBlocksMax = 256;
 constexpr int kBinMatrix = 1 << 21;
