@@ -1,6 +1,6 @@
 """MI355X-native relightable Gaussian-splat rasterizer (drop-in for r3dg_rasterization._C).
 
-`relightable3dgaussian_amd._C` is the pybind module built from csrc/torch_ext.cpp on top of
+`relightable3dgaussian_amd._C` is the pybind module built from csrc/binding/ on top of
 lib/libr3dg_hip.so (HIP kernels for gfx950 + the C ABI in include/r3dg_hip.h). There is no
 CPU fallback: importing `_C` raises if the extension has not been built, and every operator
 requires GPU tensors.

@@ -28,6 +28,9 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 HIP_SOURCES = ["preprocess.hip", "render_fwd.hip", "render_bwd.hip", "brdf.hip", "shaders.hip", "rasterizer.hip",
                "optim.hip", "bvh.hip", "knn.hip", "loss.hip", "reg_loss.hip", "relight.hip", "visibility.hip",
                "activation.hip", "compose.hip"]
+# the torch binding: binding.h is shared, module.cpp holds PYBIND11_MODULE, the others one operator family each
+BINDING = os.path.join(CSRC, "binding")
+BINDING_SOURCES = ["module.cpp", "rasterizer.cpp", "render_equation.cpp", "training.cpp", "losses.cpp", "bvh.cpp"]
 HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-result",
              "-munsafe-fp-atomics", f"-I{INC}", f"-I{CSRC}"]
 # the key path (projection, radius, rect) must not contract a*b+c into fma: see preprocess.hip
@@ -106,35 +109,43 @@ def build_hip(jobs: int = 8) -> str:
     return so
 
 
-def build_torch_ext() -> str:
-    """pybind module `_C` (csrc/torch_ext.cpp) linked against libr3dg_hip.so."""
+def build_torch_ext(jobs: int = 8) -> str:
+    """pybind module `_C` (csrc/binding/: one source per operator family) linked against libr3dg_hip.so.
+
+    A binding object depends on its source, the shared binding.h and the C ABI header only: the kernels'
+    headers are not its business."""
     import torch
     from torch.utils import cpp_extension
 
-    src = os.path.join(CSRC, "torch_ext.cpp")
-    so = os.path.join(LIB, "_C.so")
-    libso = os.path.join(LIB, "libr3dg_hip.so")
-    if not _newer(so, [src, libso] + _headers() + [__file__]):
-        return so
-    inc = cpp_extension.include_paths() + [sysconfig.get_paths()["include"], INC, CSRC,
-                                           os.path.join(ROCM, "include")]
+    os.makedirs(OBJ, exist_ok=True)
+    os.makedirs(LIB, exist_ok=True)
+    inc = cpp_extension.include_paths() + [sysconfig.get_paths()["include"], INC, os.path.join(ROCM, "include")]
     abi = int(torch._C._GLIBCXX_USE_CXX11_ABI)
-    tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
-    cmd = ["g++", "-O2", "-std=c++17", "-fPIC", "-shared", src, "-o", so,
-           "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=_C",
-           "-DTORCH_API_INCLUDE_EXTENSION_H", f"-D_GLIBCXX_USE_CXX11_ABI={abi}",
-           "-Wno-deprecated-declarations"]
-    cmd += [f"-I{p}" for p in inc]
-    cmd += [f"-L{LIB}", "-lr3dg_hip", f"-L{tlib}", "-ltorch", "-ltorch_cpu", "-ltorch_python",
-            "-lc10", "-lc10_hip", "-ltorch_hip", f"-Wl,-rpath,$ORIGIN", f"-Wl,-rpath,{tlib}"]
-    _run(cmd)
+    flags = ["-O2", "-std=c++17", "-fPIC", "-D__HIP_PLATFORM_AMD__=1", "-DUSE_ROCM=1", "-DTORCH_EXTENSION_NAME=_C",
+             "-DTORCH_API_INCLUDE_EXTENSION_H", f"-D_GLIBCXX_USE_CXX11_ABI={abi}", "-Wno-deprecated-declarations"]
+    flags += [f"-I{p}" for p in inc]
+    deps = [os.path.join(BINDING, "binding.h"), os.path.join(INC, "r3dg_hip.h"), __file__]
+    objs, cmds = [], []
+    for src in BINDING_SOURCES:
+        s = os.path.join(BINDING, src)
+        o = os.path.join(OBJ, "binding_" + src.replace(".cpp", ".o"))
+        objs.append(o)
+        if _newer(o, [s] + deps):
+            cmds.append(["g++", "-c", s, "-o", o] + flags)
+    with ThreadPoolExecutor(max(1, jobs)) as ex:
+        list(ex.map(_run, cmds))
+    so = os.path.join(LIB, "_C.so")
+    if _newer(so, objs + [os.path.join(LIB, "libr3dg_hip.so")]):
+        tlib = os.path.join(os.path.dirname(torch.__file__), "lib")
+        _run(["g++", "-shared", "-o", so, *objs, f"-L{LIB}", "-lr3dg_hip", f"-L{tlib}", "-ltorch", "-ltorch_cpu",
+              "-ltorch_python", "-lc10", "-lc10_hip", "-ltorch_hip", "-Wl,-rpath,$ORIGIN", f"-Wl,-rpath,{tlib}"])
     return so
 
 
 def build(jobs: int = 8, torch_ext: bool = True) -> None:
     build_hip(jobs)
     if torch_ext:
-        build_torch_ext()
+        build_torch_ext(jobs)
 
 
 if __name__ == "__main__":

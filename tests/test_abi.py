@@ -144,17 +144,110 @@ def test_settings_fields_match_reference():
     assert GaussianRasterizationSettings._fields == REFERENCE_SETTINGS_FIELDS
 
 
-def test_no_cpu_fallback():
-    """The product path refuses CPU tensors loudly instead of computing on the host."""
+# bound names that take no tensor, and the two that take host data by design
+NO_TENSOR_FUNCTIONS = {
+    "GetSplatShaderAddressMap", "GetShShaderAddressMap", "GetPostProcessShaderAddressMap", "EncodeTextureMode",
+    "EncodeWrapMode", "UploadTexturesToDevice", "feature_groups", "shader_manager_info", "abi_version", "get_options",
+    "set_options", "image_loss_window", "profile_enable", "profile_read"}
+HOST_DATA_FUNCTIONS = {"AllocateTexture", "create_shader_manager"}
+
+
+def _host_calls():
+    """{bound name: a well-shaped argument list, every tensor on the host}."""
     import torch
 
+    P, H, W, S, M, Ns, R = 4, 8, 8, 3, 16, 6, 5
+
+    def f(*shape):
+        return torch.zeros(*shape)
+
+    def i32(*shape):
+        return torch.zeros(*shape, dtype=torch.int32)
+
+    eye, state = torch.eye(4), torch.zeros(256, dtype=torch.uint8)
+    backward = (f(3), f(P, 3), f(P, S), i32(P), f(0), f(P, 3), f(P, 4), 1.0, f(0), eye, eye, 1.0, 1.0, f(3, H, W),
+                f(1, H, W), f(1, H, W), f(S, H, W), f(P, M, 3), 3, f(3), state, 0, state, state, True, False)
+    brdf = (f(P, 3), f(P, 1), f(P, 1), f(P, 3), f(P, 3), f(P, M, 3), f(1, M, 3), f(P, M, 1))
+    widths, roles, groups = [3, 3, 4, 1], [0, 1, 2, 3], [-1] * 10
+    n = P * sum(widths)
+    layout = (P, widths, roles)
+    one, three = f(1, H, W), f(3, H, W)
+    maps = [one, one, three, three, three, one, one, three, one, one, three]
+    vis = (f(P, 1, 1), f(P, M - 1, 1), f(P, 3), f(P), None)
+    nodes, aabbs = i32(2 * P - 1, 5), f(2 * P - 1, 6)
+    gaussians = (f(P, 3), f(P, 6), f(P))
+    return {
+        "rasterize_gaussians": (f(3), 0.0, 0.0, f(P, 3), f(P, S), f(0), f(P, 1), f(P, 3), f(P, 4), 1.0, f(0), eye, eye,
+                                eye, eye, 1.0, 1.0, 4.0, 4.0, H, W, f(P, M, 3), 3, f(3), False, False, None, None, None,
+                                None, False),
+        "rasterize_gaussians_backward": backward,
+        "rasterize_gaussians_backward_ex": backward + (H, W),
+        "rasterize_gaussians_backward_chunked": backward + (H, W, True, True, 1, None),
+        "rasterize_gaussians_backward_chunked_packed": backward + (H, W, True, True, 1, None),
+        "mark_visible": (f(P, 3), eye, eye),
+        "PreprocessModel": (f(P, 3),),
+        "rasterizer_state": (state, state, state, P, H, W, 0),
+        "sh_color_grads": (state, P, f(P, 3), 0, P),
+        "sh_grad_from_views": (f(P, 3), f(2, 3), f(2, P, 3), 3, 0, f(P, M, 3)),
+        "render_equation_forward": brdf + (Ns, False, False),
+        "render_equation_forward_with_rand": brdf + (Ns, False, f(P, Ns, 1)),
+        "render_equation_forward_complex": brdf + (Ns,),
+        "render_equation_backward": brdf + (Ns, f(P, Ns, 3), f(P, 3), f(P, 3), False),
+        "render_equation_relight": brdf + (Ns, 1, None, None, None),
+        "envmap_direct_light": (f(R, 3), f(4, 8, 3), None),
+        "adam_step": layout + (f(n), f(n), f(n), f(n), 0, n, [1e-3] * 4, 0.9, 0.999, 1e-15, 1),
+        "adam_step_groups": layout + (f(n), f(n), f(n), f(n), 0, n, [1e-3] * 4, 0.9, 0.999, 1e-15, [1] * 4),
+        "densification_stats": (f(P, 3), f(0), i32(P), f(P, 1), f(P, 1), f(P, 1), f(P)),
+        "densify_and_prune": layout + (f(n), f(n), f(n), f(P, 1), f(P, 1), f(P, 1), f(0), 0.1, 0.1, 0.01, 1.0, 0.005,
+                                       0.0, 2, False, f(0)),
+        "reset_opacity": layout + (f(n), f(n), f(n)),
+        "activate_forward": layout + (groups, f(n), None, False),
+        "activate_backward": layout + (groups, f(n), None, [None] * 12, f(n), False),
+        "set_transform": layout + (-1, f(n), None, 0),
+        "compose_object": layout + (groups, f(n), None, 0, [None] * 13, 0),
+        "render_points": (f(P, 3), f(P, 3), eye, f(3, 3), H, W, None, [0.0, 0.0, 0.0], False),
+        "image_loss_forward": (three, three, False, True),
+        "image_loss_backward": (three, three, False, f(3, 3, H, W), f(3), f(3), None),
+        "reg_loss_forward": (maps, H, W, 255, False),
+        "reg_loss_backward": (maps, H, W, 255, False, i32(1), f(8), None, 63),
+        "visibility_sh_loss_forward": vis + (None,),
+        "visibility_sh_loss_backward": vis + (None, f(1)),
+        "visibility_sh_fit_step": vis + (f(P, 1, 1), f(P, M - 1, 1), f(P, 1, 1), f(P, M - 1, 1), 1, 1e-3, 0.9, 0.999,
+                                         1e-8, f(4), 0),
+        "create_bvh": (f(P, 3), f(P, 3), f(P, 4), nodes, aabbs),
+        "trace_bvh": (nodes, aabbs, f(R, 3), f(R, 3)) + gaussians,
+        "trace_bvh_opacity": (nodes, aabbs, f(R, 3), f(R, 3)) + gaussians + (f(P, 3),),
+        "trace_bvh_opacity_centres": (nodes, aabbs, None) + gaussians + (f(P, 3),),
+        "bvh_leaf_aabbs": (f(P, 3), f(P, 3), f(P, 4)),
+        "fibonacci_dirs": (f(P, 3), 4),
+        "distCUDA2": (f(8, 3),),
+    }
+
+
+def test_host_call_table_covers_every_bound_function():
     import relightable3dgaussian_amd as r
 
-    with pytest.raises(Exception):
-        r._C.mark_visible(torch.zeros(4, 3), torch.eye(4), torch.eye(4))
-    with pytest.raises(Exception):
-        r._C.render_equation_forward(*[torch.zeros(2, 3)] * 5, torch.zeros(2, 4, 3), torch.zeros(1, 4, 3),
-                                     torch.zeros(2, 4, 1), 24, False, False)
+    bound = {n for n in dir(r._C) if not n.startswith("_") and callable(getattr(r._C, n))}
+    assert bound == set(_host_calls()) | NO_TENSOR_FUNCTIONS | HOST_DATA_FUNCTIONS
+
+
+def test_host_tensors_refused_before_any_hip_call():
+    """There is no CPU path: every bound function that takes a tensor refuses well-shaped host tensors with
+    its own check ("... must be a GPU tensor ..."), not with whatever the HIP runtime says when a host
+    pointer or a host device index reaches it."""
+    import relightable3dgaussian_amd as r
+
+    wrong = {}
+    for name, args in sorted(_host_calls().items()):
+        try:
+            getattr(r._C, name)(*args)
+            wrong[name] = "no error"
+        except RuntimeError as e:
+            if "GPU tensor" not in str(e):
+                wrong[name] = str(e).splitlines()[0]
+        except Exception as e:  # any other type is not the binding's own refusal
+            wrong[name] = f"{type(e).__name__}: {e}"
+    assert not wrong, wrong
 
 
 def test_product_package_never_imports_oracle():
