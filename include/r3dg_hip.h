@@ -888,6 +888,75 @@ int r3dg_reg_loss_backward(const r3dg_reg_loss_inputs* in, const int32_t* depth_
                            const float* weights /* [R3DG_REG_TERMS] */, const float* scale /* [1] or NULL */,
                            const r3dg_reg_loss_grads* out, r3dg_stream_t stream);
 
+/* ---- PBR image head and light regulariser (reference: gaussian_renderer/neilf.py:169-175, 278-283) -- */
+
+/* The composite over the background and the tone step between the rasterizer's feature output and the
+ * image loss (neilf.py:169-175; scene/gamma_trans.py:45-51 hdr2ldr; the captures' composite of
+ * relighting.py:225-229; the evaluation grid's clamp and the ACES hdr2ldr of
+ * utils/graphics_utils.py:197-201), one launch:
+ *   x = pbr + (1 - opacity) * bg      three float32 operations, each rounded on its own
+ *   TONE_NONE   y = x
+ *   TONE_GAMMA  y = clamp(x, lo, 1) ** gamma[0], lo = (float)1e-9, gamma a device float (never read on
+ *               the host)
+ *   TONE_ACES   s = x * 0.666667; y = (s (2.51 s + 0.03)) / (s (2.43 s + 0.59) + 0.14), the constants
+ *               rounded to float32                                                    (forward only)
+ *   TONE_CLAMP  y = clamp(x, 0, 1)                                                    (forward only)
+ * A NaN x gives a NaN y in every mode, as torch.clamp passes it on. TONE_NONE and TONE_CLAMP use exactly
+ * rounded operations only: their y is torch's bit for bit.
+ *
+ * All maps are dense: LAYOUT_HWC is pixel-major, pbr [H*W, 3] (the rasterizer's block as it is: no
+ * alignment beyond 4 bytes is assumed) and opacity [H*W]; LAYOUT_CHW is planar, pbr [3, H*W] and opacity
+ * [H*W]. bg is 3 floats, or with bg_per_pixel != 0 an image in pbr's shape and layout (the environment
+ * behind the object). image, dL_dimage and dL_dpbr have pbr's shape and layout, dL_dopacity opacity's.
+ * The layout flag fixes every address, so there are no strides.
+ *
+ * backward (TONE_NONE or TONE_GAMMA), with G = dL_dimage and xc the clamped x:
+ *   dL/dx = G                                   TONE_NONE
+ *   dL/dx = G * gamma * xc ** (gamma - 1)       TONE_GAMMA where lo <= x <= 1 (bounds included), else 0
+ *   dL_dpbr = dL/dx;  dL_dopacity = -sum_c dL/dx_c * bg_c;  bg gets no gradient
+ *   dL_dgamma [1] = sum over all elements of G * y * ln(xc), clamped elements included (ln(lo) at lo, 0
+ *   at 1), from per-workgroup partial sums added in a fixed order in f64 by a second small launch: two
+ *   runs give the same bits. No float atomics.
+ * Each of dL_dpbr, dL_dopacity, dL_dgamma may be NULL (not wanted; all three NULL: R3DG_OK, nothing
+ * launched). Nothing is saved by the forward: both calls take the same inputs; TONE_NONE reads neither
+ * pbr, opacity nor gamma (they may be NULL). Launches: forward 1, backward 1, or 2 with dL_dgamma.
+ * Scratch from scratch_alloc (only with dL_dgamma): 8 B per 1024 pixels.
+ *
+ * Checked before any device work, R3DG_ERR_ARG: an unknown layout or tone (backward: a forward-only
+ * tone), H or W < 1, H*W > INT32_MAX, a NULL required pointer, dL_dgamma without TONE_GAMMA, dL_dgamma
+ * with a NULL scratch_alloc. Everything is enqueued on stream, with no host synchronisation. */
+enum { R3DG_PBR_TONE_NONE = 0, R3DG_PBR_TONE_GAMMA = 1, R3DG_PBR_TONE_ACES = 2, R3DG_PBR_TONE_CLAMP = 3 };
+enum { R3DG_PBR_LAYOUT_CHW = 0, R3DG_PBR_LAYOUT_HWC = 1 };
+int r3dg_pbr_head_forward(int H, int W, int layout, int tone, const float* pbr, const float* opacity,
+                          const float* bg, int bg_per_pixel, const float* gamma /* [1] or NULL */,
+                          float* image, r3dg_stream_t stream);
+int r3dg_pbr_head_backward(int H, int W, int layout, int tone, const float* pbr, const float* opacity,
+                           const float* bg, int bg_per_pixel, const float* gamma /* [1] or NULL */,
+                           const float* dL_dimage, float* dL_dpbr, float* dL_dopacity,
+                           float* dL_dgamma /* [1] */, r3dg_alloc_fn scratch_alloc, void* scratch_ctx,
+                           r3dg_stream_t stream);
+
+/* The lambda_light term of calculate_loss (neilf.py:278-283): with d = diffuse_light [P, 3] dense and m
+ * the mean of a row's three channels,
+ *   loss [1] = sum over the 3 P elements of |d_c - m| / (3 P).
+ * The mean, the distances and their signs are evaluated in f64 from the float32 inputs, so a row of
+ * equal channels contributes exactly 0; per-workgroup partial sums are added in a fixed order in f64 by
+ * a second small launch and rounded once: two runs give the same bits. No float atomics. Scratch from
+ * scratch_alloc: 8 B per 1024 rows.
+ *
+ * backward: with s_c = sign(d_c - m), sign(0) = 0,
+ *   grad [P, 3] = upstream[0] * (s_c - (s_0 + s_1 + s_2) / 3) / (3 P),
+ * dense, which is the dL_ddiffuse_light r3dg_render_equation_backward takes. upstream is a device
+ * float. One launch.
+ *
+ * P < 0, a NULL pointer or a NULL scratch_alloc: R3DG_ERR_ARG before any device work. P == 0: R3DG_OK,
+ * nothing launched, allocated or written. Everything is enqueued on stream, with no host
+ * synchronisation. */
+int r3dg_light_loss_forward(int P, const float* diffuse_light, float* loss /* [1] */,
+                            r3dg_alloc_fn scratch_alloc, void* scratch_ctx, r3dg_stream_t stream);
+int r3dg_light_loss_backward(int P, const float* diffuse_light, const float* upstream /* [1] */,
+                             float* grad /* [P,3] */, r3dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

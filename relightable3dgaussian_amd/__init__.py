@@ -29,6 +29,10 @@ directions from the flat parameter buffer, and their backward into the flat grad
 `relightable3dgaussian_amd.compose` is the relighting script's scene composition (`set_transform`,
 `compose_scene`, `load_scene`: relighting.py `scene_composition`), and `relight.render_points` its
 `points` capture.
+
+`relightable3dgaussian_amd.pbr` is the PBR image head (`pbr_image`: the composite over the background and
+the tone step between the rasterizer and the image loss, neilf.py:169-175) and the `lambda_light` term
+(`light_loss`, neilf.py:278-283).
 """
 from __future__ import annotations
 

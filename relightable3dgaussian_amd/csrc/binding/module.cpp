@@ -13,7 +13,8 @@
 //       (rasterize_gaussians_backward_ex / _chunked / _chunked_packed, render_equation_forward_with_rand,
 //       rasterizer_state, feature_groups, create_shader_manager, shader_manager_info), and the operators
 //       the reference leaves to torch or to other extensions: the training step, the losses, relighting,
-//       the BVH tracer (bvh_tracing._C) and the nearest-neighbour distances (simple_knn._C).
+//       the BVH tracer (bvh_tracing._C) and the nearest-neighbour distances (simple_knn._C);
+//   (4) the submodule `_C.pbr`: the PBR image head and the light regulariser (pbr.cpp).
 // Errors from the C ABI surface as RuntimeError with the library's message.
 #include <pybind11/pybind11.h>
 
@@ -24,6 +25,7 @@ void bind_render_equation(py::module_& m);  // render_equation.cpp
 void bind_training(py::module_& m);         // training.cpp
 void bind_losses(py::module_& m);           // losses.cpp
 void bind_bvh(py::module_& m);              // bvh.cpp
+void bind_pbr(py::module_& m);              // pbr.cpp (the submodule _C.pbr)
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "MI355X-native relightable Gaussian-splat rasterizer (drop-in for r3dg_rasterization._C)";
@@ -32,4 +34,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     bind_training(m);
     bind_losses(m);
     bind_bvh(m);
+    bind_pbr(m);
 }
