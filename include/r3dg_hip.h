@@ -957,6 +957,83 @@ int r3dg_light_loss_forward(int P, const float* diffuse_light, float* loss /* [1
 int r3dg_light_loss_backward(int P, const float* diffuse_light, const float* upstream /* [1] */,
                              float* grad /* [P,3] */, r3dg_stream_t stream);
 
+/* ---- display and capture head (gui.py:138-172, relighting.py:222-230 with torchvision's save_image,
+ * train.py:243-272) and the environment background (neilf_composite.py:209-215, scene/cameras.py:87-99) ----
+ * Added within ABI 2: nothing existing changes.
+ *
+ * r3dg_display_frame turns the rasterizer's buffers into the K images a frame shows or saves, out
+ * [K, H*W, 3], in one launch. Per spec k and pixel, with s the source value (a one-channel source gives
+ * three equal channels), o = opacity, b = bg, every operation float32 and rounded on its own:
+ *   MODE_PLAIN        y = s
+ *   MODE_OVER         y = s + (1 - o) * b                        relighting.py:229
+ *   MODE_NORMAL_OVER  y = (s * 0.5 + 0.5) + (1 - o) * b          relighting.py:226-227
+ *   MODE_NORMAL_MASK  y = s * 0.5 + 0.5 * o                      gui.py:167, train.py:249-250
+ *   MODE_RANGE        y = (s - mn) / (mx - mn)                   gui.py:145, train.py:248; mn, mx the minimum
+ *                     and maximum over every element of that spec's source; a NaN anywhere in the source
+ *                     makes mn and mx NaN (torch.min / torch.max), so every y of the spec; mx == mn gives
+ *                     what the division gives
+ *   MODE_COUNT        y = (float)min(s, 1000) / 1000             gui.py:147; the source is int32
+ * then the tone:  TONE_NONE y | TONE_CLAMP clamp(y, 0, 1), a NaN stays NaN | TONE_ACES the hdr2ldr of
+ * r3dg_pbr_head_forward's TONE_ACES (the same device function),
+ * then the encoding:
+ *   ENC_F32  out is float32 and holds y
+ *   ENC_U8   out is uint8 and holds floor(clamp(y * 255 + 0.5, 0, 255)) (save_image's
+ *            mul(255).add_(0.5).clamp_(0, 255).to(uint8)); NaN gives 0 (the reference's cast of NaN is
+ *            undefined)
+ * Every mode but the ACES tone uses exactly rounded operations only: their out is torch's bit for bit.
+ *
+ * A source is dense: channels 1 ([H*W]) or 3; three channels are pixel-major [H*W, 3] with
+ * R3DG_PBR_LAYOUT_HWC (the rasterizer's block as it is: no alignment beyond 4 bytes is assumed) or planar
+ * [3, H*W] with R3DG_PBR_LAYOUT_CHW. opacity is [H*W], read by MODE_OVER, _NORMAL_OVER and _NORMAL_MASK, once
+ * per pixel for all specs. bg is read by MODE_OVER and _NORMAL_OVER: BG_VECTOR 3 device floats, BG_IMAGE a
+ * device [H*W, 3] image (r3dg_env_background's result), BG_HOST 3 HOST floats read during the call and passed
+ * to the kernel by value.
+ *
+ * Launches: 1, plus 2 when any spec is MODE_RANGE, however many are: per-workgroup (min, max) partials of
+ * all range specs, then one workgroup that finishes them into scratch the main kernel reads. Scratch from
+ * scratch_alloc (only with MODE_RANGE): 128 B, and 12 B per 1024 elements of the largest range source for
+ * every range spec. Min and max do not depend on
+ * the order, so two runs give the same bits. Everything is enqueued on stream, with no host synchronisation.
+ *
+ * Checked before any device work, R3DG_ERR_ARG: H or W < 1, H*W > INT32_MAX, n_specs outside
+ * 1..R3DG_DISPLAY_MAX_SPECS, a NULL specs, out or source, channels other than 1 or 3, an unknown layout,
+ * mode, tone, encoding or bg_kind, a bg_kind other than BG_NONE with a NULL bg, a mode that reads opacity
+ * or bg without it, MODE_RANGE with a NULL scratch_alloc. */
+enum { R3DG_DISPLAY_MODE_PLAIN = 0, R3DG_DISPLAY_MODE_OVER = 1, R3DG_DISPLAY_MODE_NORMAL_OVER = 2,
+       R3DG_DISPLAY_MODE_NORMAL_MASK = 3, R3DG_DISPLAY_MODE_RANGE = 4, R3DG_DISPLAY_MODE_COUNT = 5 };
+enum { R3DG_DISPLAY_TONE_NONE = 0, R3DG_DISPLAY_TONE_CLAMP = 1, R3DG_DISPLAY_TONE_ACES = 2 };
+enum { R3DG_DISPLAY_ENC_F32 = 0, R3DG_DISPLAY_ENC_U8 = 1 };
+enum { R3DG_DISPLAY_BG_NONE = 0, R3DG_DISPLAY_BG_VECTOR = 1, R3DG_DISPLAY_BG_IMAGE = 2, R3DG_DISPLAY_BG_HOST = 3 };
+#define R3DG_DISPLAY_MAX_SPECS 16
+typedef struct r3dg_display_spec {
+    const void* source; /* float32, or int32 with MODE_COUNT */
+    int channels;       /* 1 or 3 */
+    int layout;         /* R3DG_PBR_LAYOUT_HWC or _CHW (the same memory for one channel) */
+    int mode;           /* R3DG_DISPLAY_MODE_* */
+    int tone;           /* R3DG_DISPLAY_TONE_* */
+} r3dg_display_spec;
+int r3dg_display_frame(int H, int W, int n_specs, const r3dg_display_spec* specs, const float* opacity,
+                       const float* bg, int bg_kind, int encoding, void* out /* [n_specs, H*W, 3] */,
+                       r3dg_alloc_fn scratch_alloc, void* scratch_ctx, r3dg_stream_t stream);
+
+/* The environment behind the object as an image, out [H*W, 3], in one launch and without a direction image:
+ * per pixel (v, u), scene/cameras.py:91-97,
+ *   d = F.normalize(((u - cx) / fx, (v - cy) / fy, 1)) (eps 1e-12), fx = K[0][0], fy = K[1][1], cx = K[0][2],
+ *   cy = K[1][2] of intrinsics K, a device [3,3];  w = R d, R the rows c2w[i * c2w_stride + 0..2], i = 0..2, of
+ *   the device camera-to-world matrix (c2w_stride 4 for a [4,4], 3 for a [3,3]),
+ * then with R3DG_LIGHT_MAP r3dg_envmap_direct_light's lookup along w (the same device function, with
+ * env_transform), or with R3DG_LIGHT_SH max(eval_sh(w) . env_shs + 0.5, 0) of env_shs [S, 3], S <= 25
+ * (neilf_composite.py:212-213; the basis and the fused sum of r3dg_render_equation_relight's R3DG_LIGHT_SH,
+ * the 0.5 added last as the reference writes it). Neither
+ * matrix is read on the host. out is a valid BG_IMAGE of r3dg_display_frame and a per-pixel bg of
+ * r3dg_pbr_head_forward (LAYOUT_HWC).
+ * R3DG_ERR_ARG before any device work: H or W < 1, H*W > INT32_MAX, a NULL intrinsics, c2w or out, a
+ * c2w_stride other than 3 or 4, a light_mode other than _SH or _MAP, _MAP without a map or with env_h or
+ * env_w < 1, _SH with S outside 1..25 or a NULL env_shs. */
+int r3dg_env_background(int H, int W, const float* intrinsics, const float* c2w, int c2w_stride, int light_mode,
+                        const float* envmap, int env_h, int env_w, const float* env_transform,
+                        const float* env_shs, int S, float* out, r3dg_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

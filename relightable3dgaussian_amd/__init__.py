@@ -33,6 +33,10 @@ directions from the flat parameter buffer, and their backward into the flat grad
 `relightable3dgaussian_amd.pbr` is the PBR image head (`pbr_image`: the composite over the background and
 the tone step between the rasterizer and the image loss, neilf.py:169-175) and the `lambda_light` term
 (`light_loss`, neilf.py:278-283).
+
+`relightable3dgaussian_amd.display` is the display and capture head (`frame_buffers`: from the rasterizer's
+buffers to the 8-bit or float32 images a GUI frame, a relighting frame's captures or the evaluation report
+shows, in one launch), and `relight.env_background` the environment behind the object as an image.
 """
 from __future__ import annotations
 

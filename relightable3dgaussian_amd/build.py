@@ -27,10 +27,11 @@ HIPCC = os.path.join(ROCM, "bin", "hipcc")
 
 HIP_SOURCES = ["preprocess.hip", "render_fwd.hip", "render_bwd.hip", "brdf.hip", "shaders.hip", "rasterizer.hip",
                "optim.hip", "bvh.hip", "knn.hip", "loss.hip", "reg_loss.hip", "relight.hip", "visibility.hip",
-               "activation.hip", "compose.hip", "pbr_head.hip"]
+               "activation.hip", "compose.hip", "pbr_head.hip", "display.hip"]
 # the torch binding: binding.h is shared, module.cpp holds PYBIND11_MODULE, the others one operator family each
 BINDING = os.path.join(CSRC, "binding")
-BINDING_SOURCES = ["module.cpp", "rasterizer.cpp", "render_equation.cpp", "training.cpp", "losses.cpp", "bvh.cpp", "pbr.cpp"]
+BINDING_SOURCES = ["module.cpp", "rasterizer.cpp", "render_equation.cpp", "training.cpp", "losses.cpp", "bvh.cpp", "pbr.cpp",
+                   "display.cpp"]
 HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-Wno-unused-result",
              "-munsafe-fp-atomics", f"-I{INC}", f"-I{CSRC}"]
 # the key path (projection, radius, rect) must not contract a*b+c into fma: see preprocess.hip
@@ -62,9 +63,14 @@ HIP_FLAGS = ["-O3", "--offload-arch=gfx950", "-fPIC", "-std=c++17", "-Wall", "-W
 # pbr_head.hip: the composite x = pbr + (1 - opacity) * bg is three torch tensor operations in the reference, each
 # rounded on its own; uncontracted, the "none" and "clamp" images are the reference's bits (a contracted
 # fma(1 - opacity, bg, pbr) rounds once and differs in the last bit), and ACES rounds where hdr2ldr does
+# display.hip: the same reason and the same tone functions (csrc/tone_device.h): every mode is two to four torch
+# tensor operations in the reference (s * 0.5 + 0.5, (1 - opacity) * bg, y * 255 + 0.5), each rounded on its own;
+# uncontracted, the float32 and the 8-bit images are the reference's bits (a contracted fma(y, 255, 0.5) moves a
+# value that sits half a float32 step under a half-way point into the next byte)
 PER_FILE_FLAGS = {"preprocess.hip": ["-ffp-contract=off"], "bvh.hip": ["-ffp-contract=off"],
                   "visibility.hip": ["-ffp-contract=off"], "activation.hip": ["-ffp-contract=off"],
                   "compose.hip": ["-ffp-contract=off"], "pbr_head.hip": ["-ffp-contract=off"],
+                  "display.hip": ["-ffp-contract=off"],
                   "knn.hip": ["-ffp-contract=off"], "loss.hip": ["-ffp-contract=off"],
                   "reg_loss.hip": ["-ffp-contract=off"], "relight.hip": ["-ffp-contract=off"],
                   "brdf.hip": ["-ffp-contract=off", "-fno-slp-vectorize"],

@@ -14,7 +14,8 @@
 //       rasterizer_state, feature_groups, create_shader_manager, shader_manager_info), and the operators
 //       the reference leaves to torch or to other extensions: the training step, the losses, relighting,
 //       the BVH tracer (bvh_tracing._C) and the nearest-neighbour distances (simple_knn._C);
-//   (4) the submodule `_C.pbr`: the PBR image head and the light regulariser (pbr.cpp).
+//   (4) the submodule `_C.pbr`: the PBR image head and the light regulariser (pbr.cpp);
+//   (5) the submodule `_C.display`: the display and capture head and the environment background (display.cpp).
 // Errors from the C ABI surface as RuntimeError with the library's message.
 #include <pybind11/pybind11.h>
 
@@ -26,6 +27,7 @@ void bind_training(py::module_& m);         // training.cpp
 void bind_losses(py::module_& m);           // losses.cpp
 void bind_bvh(py::module_& m);              // bvh.cpp
 void bind_pbr(py::module_& m);              // pbr.cpp (the submodule _C.pbr)
+void bind_display(py::module_& m);          // display.cpp (the submodule _C.display)
 
 PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     m.doc() = "MI355X-native relightable Gaussian-splat rasterizer (drop-in for r3dg_rasterization._C)";
@@ -35,4 +37,5 @@ PYBIND11_MODULE(TORCH_EXTENSION_NAME, m) {
     bind_losses(m);
     bind_bvh(m);
     bind_pbr(m);
+    bind_display(m);
 }

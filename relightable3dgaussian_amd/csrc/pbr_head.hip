@@ -31,6 +31,7 @@
 // Built with -ffp-contract=off: the composite's three operations round one at a time, as torch's do, so the
 // "none" and "clamp" forwards are the reference's bits.
 #include "act_device.h"
+#include "tone_device.h"  // clampf, aces (shared with display.hip)
 
 namespace r3dg {
 namespace {
@@ -77,15 +78,6 @@ __device__ __forceinline__ void load_bg(const float* bg, long long n, long long 
 #pragma unroll
         for (int r = 0; r < kQuad; ++r) b[3 * r] = b0, b[3 * r + 1] = b1, b[3 * r + 2] = b2;
     }
-}
-
-// a NaN stays a NaN, as through torch.clamp (fminf / fmaxf would drop it)
-__device__ __forceinline__ float clampf(float x, float lo, float hi) { return x < lo ? lo : (x > hi ? hi : x); }
-
-// utils/graphics_utils.py:197-201 hdr2ldr, its Python constants rounded to float32 where they meet the tensor
-__device__ __forceinline__ float aces(float x) {
-    const float s = x * 0.666667f;
-    return (s * (2.51f * s + 0.03f)) / (s * (2.43f * s + 0.59f) + 0.14f);
 }
 
 template <bool HWC, bool BGIMG>

@@ -301,6 +301,45 @@ __global__ void __launch_bounds__(256) envmap_light_kernel(int nd, const float* 
     light[3 * i] = o.x; light[3 * i + 1] = o.y; light[3 * i + 2] = o.z;
 }
 
+// The environment behind the object (neilf_composite.py:209-215) without the direction image of
+// Camera.get_world_directions (scene/cameras.py:87-99): one lane per pixel forms its direction from the
+// intrinsics K and the rotation rows of c2w, both read on the device, and looks the light up. MAP: env_lookup,
+// the function envmap_light_kernel runs; else clamp_min(eval_sh + 0.5, 0) of shs [S, 3] with the basis and
+// the fused sum of relight_kernel's kLightSH branch.
+template <bool MAP>
+__global__ void __launch_bounds__(256) env_background_kernel(int H, int W, const float* __restrict__ K,
+                                                             const float* __restrict__ c2w, int stride,
+                                                             const float* __restrict__ map, int eh, int ew,
+                                                             const float* __restrict__ T,
+                                                             const float* __restrict__ shs, int S,
+                                                             float* __restrict__ out) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= (size_t)H * W) return;
+    const int v = (int)(i / W), u = (int)(i - (size_t)v * W);
+    const float fx = K[0], cx = K[2], fy = K[4], cy = K[5];
+    const float c[3] = {((float)u - cx) / fx, ((float)v - cy) / fy, 1.0f};
+    const float nrm = fmaxf(sqrtf((c[0] * c[0] + c[1] * c[1]) + c[2] * c[2]), 1e-12f);  // F.normalize
+    const float d0 = c[0] / nrm, d1 = c[1] / nrm, d2 = c[2] / nrm;
+    const float3 w = make_float3((c2w[0] * d0 + c2w[1] * d1) + c2w[2] * d2,
+                                 (c2w[stride] * d0 + c2w[stride + 1] * d1) + c2w[stride + 2] * d2,
+                                 (c2w[2 * stride] * d0 + c2w[2 * stride + 1] * d1) + c2w[2 * stride + 2] * d2);
+    float o[3];
+    if constexpr (MAP) {
+        const float3 g = env_lookup(map, eh, ew, T, w);
+        o[0] = g.x; o[1] = g.y; o[2] = g.z;
+    } else {
+        float coef[kRelightMaxSH];
+        sh_coef25(w.x, w.y, w.z, coef);
+        // the 0.5 is added last, as the reference writes it (eval_sh(...) + 0.5): started from 0.5, as the kLightSH
+        // branch starts, every partial sum is larger and the 16 or 25 roundings with it (measured on one pixel at
+        // degree 3: 2.4e-7 of the value against 1.7e-7)
+        sh_dot<0, 3>(coef, shs, S, 0.0f, o);
+#pragma unroll
+        for (int k = 0; k < 3; ++k) o[k] = fmaxf(o[k] + 0.5f, 0.0f);
+    }
+    out[3 * i] = o[0]; out[3 * i + 1] = o[1]; out[3 * i + 2] = o[2];
+}
+
 template <int LIGHT, bool TRACED>
 static hipError_t launch_relight2(const RelightKArgs& a, hipStream_t st) {
     const r3dg_brdf_inputs& in = a.in;
@@ -379,6 +418,33 @@ extern "C" int r3dg_envmap_direct_light(int n, const float* dirs, const float* e
     hipLaunchKernelGGL(envmap_light_kernel, dim3((unsigned)(((size_t)n + 255) / 256)), dim3(256), 0, (hipStream_t)stream, n, dirs,
                        envmap,
                        env_h, env_w, env_transform, light);
+    R3DG_CHECK_HIP(hipGetLastError());
+    return R3DG_OK;
+}
+
+extern "C" int r3dg_env_background(int H, int W, const float* intrinsics, const float* c2w, int c2w_stride,
+                                   int light_mode, const float* envmap, int env_h, int env_w,
+                                   const float* env_transform, const float* env_shs, int S, float* out,
+                                   r3dg_stream_t stream) {
+    R3DG_REQUIRE(H >= 1 && W >= 1, "env_background: H, W >= 1 expected");
+    R3DG_REQUIRE((long long)H * W <= 0x7fffffffll, "env_background: H * W exceeds int32");
+    R3DG_REQUIRE(intrinsics && c2w && out, "env_background: intrinsics, c2w or out is NULL");
+    R3DG_REQUIRE(c2w_stride == 3 || c2w_stride == 4, "env_background: c2w_stride must be 3 or 4");
+    R3DG_REQUIRE(light_mode == R3DG_LIGHT_SH || light_mode == R3DG_LIGHT_MAP,
+                 "env_background: light_mode must be R3DG_LIGHT_SH or _MAP");
+    const dim3 grid((unsigned)(((size_t)H * W + 255) / 256)), block(256);
+    hipStream_t st = (hipStream_t)stream;
+    if (light_mode == R3DG_LIGHT_MAP) {
+        int rc = check_envmap(envmap, env_h, env_w, "env_background");
+        if (rc) return rc;
+        hipLaunchKernelGGL(env_background_kernel<true>, grid, block, 0, st, H, W, intrinsics, c2w, c2w_stride, envmap,
+                           env_h, env_w, env_transform, env_shs, S, out);
+    } else {
+        R3DG_REQUIRE(env_shs && S >= 1 && S <= kRelightMaxSH,
+                     "env_background: the environment SH needs a pointer and 1 to 25 coefficients (degree 4)");
+        hipLaunchKernelGGL(env_background_kernel<false>, grid, block, 0, st, H, W, intrinsics, c2w, c2w_stride, envmap,
+                           env_h, env_w, env_transform, env_shs, S, out);
+    }
     R3DG_CHECK_HIP(hipGetLastError());
     return R3DG_OK;
 }

@@ -18,6 +18,8 @@ chunk loop over `rendering_equation_python` and the `torch.cat` of nine tensors
               (pc._visibility_tracing); without it a ValueError, as the reference raises
 `render_points(xyz, color, world_view_transform, intrinsics, H, W, bg, return_depth=False)` is the script's
 `points` capture (relighting.py:89-123), a z-buffered point cloud (csrc/compose.hip `r3dg_render_points`).
+`env_background(light, intrinsics, c2w, H, W)` -> [H, W, 3] is the environment behind the object
+(neilf_composite.py:209-215) in one launch, without the direction image (`r3dg_env_background`).
 
 Each SH width is 0..25. Forward only: the relighting script runs under torch.no_grad(). No CPU path and
 no torch fallback: the extension rejects CPU tensors.
@@ -78,6 +80,42 @@ def render_equation_relight(base_color, roughness, metallic, normals, viewdirs, 
     extra_results = {k: cols[k] for k in ["incident_lights", "local_incident_lights", "global_incident_lights",
                                           "incident_visibility"]}
     return cols["rgb"], extra_results, features
+
+
+@torch.no_grad()
+def env_background(light, intrinsics: torch.Tensor, c2w: torch.Tensor, H: int, W: int) -> torch.Tensor:
+    """The environment behind the object (neilf_composite.py:209-215) -> [H, W, 3], in one launch and without
+    the [3, H, W] direction image of `Camera.get_world_directions()` (scene/cameras.py:87-99): per pixel (v, u)
+    d = normalize(((u - cx) / fx, (v - cy) / fy, 1)) with F.normalize's eps, then c2w[:3, :3] @ d. `light` is an
+    `EnvLight` (the lookup `direct_light` runs, with `light.transform`) or the environment SH [1, M, 3],
+    M = (deg + 1)^2 <= 25 (`clamp_min(eval_sh(deg, shs, d) + 0.5, 0)`). `intrinsics` [3, 3] and `c2w` [4, 4] or
+    [3, 3] are device tensors, read on the device. The result is a valid `bg` image of `display.frame_buffers`
+    and of `pbr.pbr_image`."""
+    who = "env_background"
+    for name, t, shapes in (("intrinsics", intrinsics, ((3, 3),)), ("c2w", c2w, ((4, 4), (3, 3)))):
+        if not isinstance(t, torch.Tensor) or t.dtype != torch.float32:
+            raise ValueError(f"{who}: {name}: a float32 tensor expected")
+        if tuple(t.shape) not in shapes:
+            raise ValueError(f"{who}: shape mismatch: {name} {' or '.join(str(list(s)) for s in shapes)} expected, "
+                             f"got {tuple(t.shape)}")
+    if int(H) < 1 or int(W) < 1:
+        raise ValueError(f"{who}: H, W >= 1 expected, got {H} x {W}")
+    envmap = transform = shs = None
+    if isinstance(light, EnvLight):
+        envmap, transform = light.envmap, light.transform
+    elif isinstance(light, torch.Tensor):
+        if light.dtype != torch.float32:
+            raise ValueError(f"{who}: light: a float32 tensor expected")
+        if light.dim() != 3 or light.shape[0] != 1 or light.shape[2] != 3 or light.shape[1] not in (1, 4, 9, 16, 25):
+            raise ValueError(f"{who}: shape mismatch: environment SH [1, M, 3] with M = (deg + 1)^2, deg <= 4 "
+                             f"expected, got {tuple(light.shape)}")
+        shs = light.detach()
+    else:
+        raise TypeError(f"{who}: light must be an EnvLight or the environment SH tensor [1, M, 3]")
+    for name, t in (("c2w", c2w), ("light", envmap if shs is None else shs), ("light.transform", transform)):
+        if t is not None and t.device != intrinsics.device:
+            raise ValueError(f"{who}: {name} is on {t.device}, intrinsics on {intrinsics.device}: one device expected")
+    return _C.display.env_background(intrinsics, c2w, int(H), int(W), envmap, transform, shs)
 
 
 @torch.no_grad()
